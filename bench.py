@@ -20,9 +20,16 @@ ranks itself (rank r on device r % devices). The headline shards by document (no
 "partitioned ... by document/topic"): every rank merges its own independent documents (seeds
 offset per rank) with no data-path collective ⇒ "scaling": "weak". Barriers, the max-over-ranks
 step time and the per-rank reports go through libycrdt's own communicator (RCCL; a host exchange
-over gloo when ranks share a device). With N > 1 two more legs run by default: C4 key-hash sharded
-across the ranks (one 102 M-item document) and the C5 fleet (routed ingest + the fleet
-state-vector all-reduce).
+over gloo when ranks share a device).
+
+A plain run (`--gpus 1 --steps N --warmup W`) does only what the headline needs: generate and
+stage the documents, W warm-up merges, N timed merges, the result line (its roofline figures come
+from the engine's phase events of the timed merges themselves). `--dump-outputs DIR` also writes
+what the last timed merge returned as .npy arrays (dump_outputs). Everything else — end to end,
+single document, CPU baselines (Yjs in Node, the oracle port), fleet sync / ingest, apply loop,
+full-state ingest, per-op, C3, C4, and with N > 1 C4 key-hash sharded across the ranks (one
+102 M-item document) and the C5 fleet (routed ingest + the fleet state-vector all-reduce) — runs
+under `--full`; `--billion DOCS` stays a leg of its own.
 """
 import argparse
 import csv
@@ -47,6 +54,13 @@ def parse():
     p.add_argument("--docs", type=int, default=112,
                    help="independent documents of the workload merged per step in one device pass (>= 100 M items)")
     p.add_argument("--replicas", type=int, default=None, help="override replica count (default: config)")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline, run every side leg too (end to end, single document, CPU baselines, fleet, "
+                        "apply loop, full-state ingest, per-op, C3, C4; N > 1: C4 sharded and the C5 fleet over the ranks); "
+                        "without it only the headline merge is set up, warmed up and timed")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed merge returned (every document's update and state vector) to "
+                        "DIR/<name>.npy (see dump_outputs)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--fleet-pairs", type=int, default=20000,
                    help="C5-shaped sync-responder leg: (doc state, peer SV) pairs in one batched diff (0 = off)")
@@ -58,13 +72,17 @@ def parse():
     p.add_argument("--fleet-docs", type=int, default=1_000_000, help="documents in the C5 fleet-ingest leg (0 = skip)")
     p.add_argument("--no-c4", action="store_true", help="skip the C4 leg (N = 1: one GPU; N > 1: key-hash sharded over the ranks)")
     p.add_argument("--only-headline", action="store_true",
-                   help="time the headline merge only (no side legs): rocprof averages then match the bench line")
+                   help="time the headline merge only, even under --full (no side legs): rocprof averages then "
+                        "match the bench line")
     p.add_argument("--c3-items", type=int, default=10_000_000,
                    help="C3 leg: YArray 'messages', 256 replicas x 16 rounds, this many values (0 = off)")
     p.add_argument("--billion", type=int, default=0, metavar="DOCS",
                    help="opt-in leg: DOCS distinct C2 documents (1120 = 1.0 B items, ~15 GB of updates) merged in ONE "
                         "ycrdt_batch_merge (multi-window batch), with its HBM footprint and properties; skips the side legs")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1 (the number of timed merges)")
+    return args
 
 
 def _sample(cfg, n_replicas, updates, gen_map):
@@ -790,6 +808,54 @@ def fleet_sync_leg(eng, n_pairs):
     return res
 
 
+DUMP_UPDATE_BYTES = 12 << 20  # update bytes written by --dump-outputs (float32: 48 MiB of the 64 MB it may take)
+DUMP_SV_BYTES = 1 << 20
+
+
+def _dump_sample(blobs, budget, seed):
+    """Every byte of `blobs` when they fit `budget`; else budget // len(blobs) bytes of each blob at
+    sorted positions drawn from a generator seeded by (seed, blob index, blob length): the same
+    outputs give the same sample in every run and every build."""
+    import numpy as np
+
+    arrs = [np.frombuffer(b, dtype=np.uint8) for b in blobs]
+    if sum(a.size for a in arrs) > budget:
+        k = max(1, budget // len(arrs))
+        arrs = [a if a.size <= k else a[np.sort(np.random.default_rng([seed, i, a.size]).integers(0, a.size, k))]
+                for i, a in enumerate(arrs)]
+    return np.concatenate(arrs).astype(np.float32) if arrs else np.zeros(0, np.float32)
+
+
+def dump_outputs(path, results, rank, world):
+    """--dump-outputs DIR: what the last timed merge returned — per document (canonical update, state
+    vector), the bytes a caller of Batch.result_docs() receives — as .npy arrays a second build's
+    run with the same arguments can be compared with, file for file:
+      update_lengths / sv_lengths   float64 [docs]     byte length of every document's update / state vector
+      update_crc32 / sv_crc32       float64 [docs]     zlib.crc32 over the whole of each (exact in float64)
+      updates / state_vectors       float32 [bytes]    the bytes themselves, document after document; beyond
+                                                       DUMP_UPDATE_BYTES / DUMP_SV_BYTES a fixed seeded sample
+                                                       of every document's bytes (_dump_sample)
+    With more than one rank every rank writes its own documents as <name>_rank<r>.npy."""
+    import zlib
+
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    tag = "" if world == 1 else f"_rank{rank}"
+    ups = [u for u, _ in results]
+    svs = [v for _, v in results]
+    arrays = {
+        "update_lengths": np.array([len(u) for u in ups], dtype=np.float64),
+        "sv_lengths": np.array([len(v) for v in svs], dtype=np.float64),
+        "update_crc32": np.array([zlib.crc32(u) for u in ups], dtype=np.float64),
+        "sv_crc32": np.array([zlib.crc32(v) for v in svs], dtype=np.float64),
+        "updates": _dump_sample(ups, DUMP_UPDATE_BYTES, 0x59435231),
+        "state_vectors": _dump_sample(svs, DUMP_SV_BYTES, 0x59435232),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f"{name}{tag}.npy"), a)
+
+
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -945,6 +1011,10 @@ def run_rank(args, report=None):
     ms_per_step = dt * 1e3 / args.steps
     value = items_step * args.steps / dt
     phases = [(n, m / args.steps) for n, m in phase_acc.items()]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, batch.result_docs() if ndocs > 1 else [batch.result()], rank, world)
+    # the side legs run under --full only (and never beside --only-headline or --billion)
+    side_legs = args.full and not args.only_headline and not args.billion
 
     # ---- roofline of the dominant kernel. Every single-kernel phase of the merge (one launch,
     # timed by the engine's HIP events on the stream it runs on) with its algorithmic bytes per
@@ -1027,7 +1097,7 @@ def run_rank(args, report=None):
     # A serving loop: batch k+1 is staged (host pack + pinned H2D on the engine's copy stream) by a
     # second host thread while batch k merges and its result comes back; one result buffer is
     # reused. One untimed warm-up batch (pinned areas, first touch of the result buffer).
-    e2e_steps = 0 if args.only_headline or args.billion or world > 1 else 4
+    e2e_steps = 4 if side_legs and world == 1 else 0
     make = (lambda: crdt_amd.Batch(docs=docs, engine=eng)) if ndocs > 1 else (lambda: crdt_amd.Batch(updates, eng))
     e2e_ms = 0.0
     if e2e_steps:
@@ -1050,7 +1120,7 @@ def run_rank(args, report=None):
     del batch
     # ---- one C2 document per step (the round-1 headline shape), for continuity
     single = None
-    if ndocs > 1 and rank == 0 and not args.only_headline and not args.billion:
+    if ndocs > 1 and rank == 0 and side_legs:
         sb = crdt_amd.Batch(updates, eng)
         sst = sb.merge()
         s0 = time.perf_counter()
@@ -1061,22 +1131,22 @@ def run_rank(args, report=None):
         del sb
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.only_headline and not args.billion:
+    side = rank == 0 and world == 1 and side_legs
+    if side and not args.no_cpu_baseline:
         cpu = cpu_baselines(args, cfg, updates, out_update, crdt_amd.Batch(updates, eng).merge(), eng, gen_map)
     fleet = None
-    if rank == 0 and world == 1 and args.fleet_pairs > 0 and not args.only_headline and not args.billion:
+    if side and args.fleet_pairs > 0:
         fleet = fleet_sync_leg(eng, args.fleet_pairs)
     ingest = None
-    if rank == 0 and world == 1 and args.fleet_docs > 0 and not args.only_headline and not args.billion:
+    if side and args.fleet_docs > 0:
         ingest = fleet_ingest_leg(eng, args.fleet_docs)
-    side = rank == 0 and world == 1 and not args.only_headline and not args.billion
     loop = apply_loop_leg(eng, updates, out_update) if side else None
     full_c2 = full_state_leg(eng, "one C2 document's merged state (1 001 clients) as one update", updates, out_update, small_ops=30) if side else None
     per_op = per_op_leg(eng) if side and not args.no_per_op else None
     c3 = c3_leg(eng, args.c3_items) if side and args.c3_items > 0 else None
     c4 = c4_leg(eng) if side and not args.no_c4 else None
-    # N > 1: the multi-GPU legs (on by default): C4 key-hash sharded over the ranks, the C5 fleet
-    multi = comm is not None and not args.only_headline and not args.billion
+    # N > 1: the multi-GPU legs (under --full): C4 key-hash sharded over the ranks, the C5 fleet
+    multi = comm is not None and side_legs
     c4s = c4_sharded_leg(eng, comm, world, rank) if multi and not args.no_c4 else None
     fleet_ranks = fleet_ranks_leg(eng, comm, world, rank, args.fleet_docs) if multi and args.fleet_docs > 0 else None
     billion = billion_leg(eng, cfg, gen_map, args.billion) if args.billion and rank == 0 else None
@@ -1087,6 +1157,7 @@ def run_rank(args, report=None):
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": bool(side_legs),
         "ms_per_step": round(ms_per_step, 4),
         "higher_is_better": True,
         "scaling": "weak",

@@ -1,6 +1,6 @@
 #!/bin/bash
-# the per-call GPU step: the round-end rehearsal (every -m gpu test, smoke, the default bench)
+# one GPU step: the rehearsal (every -m gpu test, smoke, bench.py --full), outputs under $OUT
 set -u
-mkdir -p gpurun_out
+export OUT=${OUT:-run_out}
 export TMPDIR=/tmp
 bash scripts/gpu_final.sh || exit 1
