@@ -70,6 +70,21 @@ class MergeStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class SyncStats(ctypes.Structure):
+    _fields_ = [
+        ("pairs_marks", ctypes.c_uint64),
+        ("pairs_walk", ctypes.c_uint64),
+        ("pairs_single", ctypes.c_uint64),
+        ("cut_structs", ctypes.c_uint64),
+        ("out_bytes", ctypes.c_uint64),
+        ("walk_max", ctypes.c_uint32),
+        ("device_ms", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 def library_path():
     # YCRDT_LIB: another build of the library (A/B experiments); the in-tree one by default
     return os.environ.get("YCRDT_LIB") or os.path.join(_HERE, "libycrdt.so")
@@ -90,6 +105,7 @@ EXPORTS = (
     "ycrdt_comm_unique_id", "ycrdt_comm_create", "ycrdt_comm_destroy", "ycrdt_batch_merge_sharded",
     "ycrdt_comm_sv_allreduce_max", "ycrdt_comm_ds_allgather", "ycrdt_comm_create_exchange", "ycrdt_route",
     "ycrdt_comm_fleet_sv_allreduce_max", "ycrdt_docs_states_packed", "ycrdt_comm_allgather", "ycrdt_device_count",
+    "ycrdt_docs_diff",
 )
 
 MERGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p)
@@ -168,6 +184,7 @@ def lib():
     L.ycrdt_comm_create_exchange.argtypes = [vp, i32, i32, P(_Exchange), P(vp)]
     L.ycrdt_docs_states_packed.argtypes = [vp, P(vp), sz, vp, ctypes.c_uint64, P(ctypes.c_uint64), P(ctypes.c_uint64)]
     L.ycrdt_route.argtypes = [ctypes.c_char_p, sz, u32]
+    L.ycrdt_docs_diff.argtypes = [vp, P(vp), P(_Buf), sz, P(_Out), P(ctypes.c_uint64), P(SyncStats)]
     L.ycrdt_route.restype = u32
     L.ycrdt_comm_fleet_sv_allreduce_max.argtypes = [vp, vp, P(u32), P(_Buf), sz, P(_Out), P(_Out), P(_Out)]
     L.ycrdt_map_size.argtypes = [vp, cs, cs, P(u32)]
@@ -728,3 +745,37 @@ def diff_updates(updates, svs, engine=None) -> list:
     outs = (_Out * max(len(ukeep), 1))()
     _check(lib().ycrdt_diff_updates(eng._h, ua, va, len(ukeep), outs))
     return [_take(outs[i]) for i in range(len(ukeep))]
+
+
+def docs_diff_stats(docs, svs, engine=None):
+    """([Y.encodeStateAsUpdate(d, sv) for d, sv in zip(docs, svs)], stats) in one device pass
+    (ycrdt_docs_diff): the sync responder of crdt.js:286-291 batched over peers and topics, answered
+    from the documents' resident states. An empty sv asks for the full state; a doc may repeat.
+    stats: ycrdt_sync_stats as a dict (which path the pairs took)."""
+    import numpy as np
+
+    if len(docs) != len(svs):
+        raise ValueError("docs_diff: one state vector per document")
+    eng = engine or (docs[0].engine if docs else default_engine())
+    hv = np.fromiter((d._h.value for d in docs), dtype=np.uint64, count=len(docs)) if docs else np.zeros(1, np.uint64)
+    hs = hv.ctypes.data_as(ctypes.POINTER(ctypes.c_void_p))
+    va, vkeep = _bufs([bytes(v) for v in svs])
+    offs = np.zeros(len(docs) + 1, dtype=np.uint64)
+    out = _Out()
+    st = SyncStats()
+    _check(lib().ycrdt_docs_diff(eng._h, hs, va, len(docs), ctypes.byref(out), offs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+                                 ctypes.byref(st)))
+    try:
+        o = offs.tolist()
+        if out.len < 4096 * len(docs):  # small replies: one copy of the blob, sliced (a ctypes call each costs more)
+            blob = ctypes.string_at(out.ptr, out.len) if out.len else b""
+            return [blob[o[i]:o[i + 1]] for i in range(len(docs))], st.as_dict()
+        # large replies: one copy each, straight out of the library's blob
+        return [ctypes.string_at(out.ptr + o[i], o[i + 1] - o[i]) for i in range(len(docs))], st.as_dict()
+    finally:
+        lib().ycrdt_free(ctypes.byref(out))
+
+
+def docs_diff(docs, svs, engine=None) -> list:
+    """[Y.encodeStateAsUpdate(d, sv) for d, sv in zip(docs, svs)] in one device pass (docs_diff_stats)."""
+    return docs_diff_stats(docs, svs, engine)[0]

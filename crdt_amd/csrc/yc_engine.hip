@@ -19,6 +19,7 @@
 #include "yc_host.h"
 #include "yc_ingest.h"
 #include "yc_comm.h"
+#include "yc_sync.h"
 #include <thread>
 #include <atomic>
 #include "../../include/ycrdt.h"
@@ -144,8 +145,9 @@ uint32_t next_pow2(uint64_t v) {
   return (uint32_t)std::min<uint64_t>(p, 1ull << 31);
 }
 
-// decode a state vector (varuint n, (client, clock) × n)
-bool parse_sv(const uint8_t* p, size_t n, std::unordered_map<uint32_t, uint32_t>& out) {
+// decode a state vector (varuint n, (client, clock) × n): put(client, clock) per entry
+template <class Put>
+bool parse_sv_each(const uint8_t* p, size_t n, Put put) {
   size_t pos = 0;
   auto vu = [&](uint32_t& v) -> bool {
     uint32_t r = 0;
@@ -164,8 +166,33 @@ bool parse_sv(const uint8_t* p, size_t n, std::unordered_map<uint32_t, uint32_t>
   for (uint32_t i = 0; i < k; ++i) {
     uint32_t c, cl;
     if (!vu(c) || !vu(cl)) return false;
-    out[c] = cl;
+    put(c, cl);
   }
+  return true;
+}
+bool parse_sv(const uint8_t* p, size_t n, std::unordered_map<uint32_t, uint32_t>& out) {
+  return parse_sv_each(p, n, [&](uint32_t c, uint32_t cl) { out[c] = cl; });
+}
+// the same as (client, clock) pairs with the clients ascending (a client named twice: its last
+// clock, as the map gives). Yjs writes state vectors in descending or store order: no hashing,
+// and no sort when the input is already in either order.
+bool parse_sv_sorted(const uint8_t* p, size_t n, std::vector<std::pair<uint32_t, uint32_t>>& v) {
+  v.clear();
+  if (!parse_sv_each(p, n, [&](uint32_t c, uint32_t cl) { v.emplace_back(c, cl); })) return false;
+  auto before = [](const std::pair<uint32_t, uint32_t>& a, const std::pair<uint32_t, uint32_t>& b) { return a.first < b.first; };
+  auto after = [](const std::pair<uint32_t, uint32_t>& a, const std::pair<uint32_t, uint32_t>& b) { return a.first > b.first; };
+  if (std::adjacent_find(v.begin(), v.end(), [&](const auto& a, const auto& b) { return !before(a, b); }) == v.end()) return true;
+  if (std::adjacent_find(v.begin(), v.end(), [&](const auto& a, const auto& b) { return !after(a, b); }) == v.end()) {
+    std::reverse(v.begin(), v.end());
+    return true;
+  }
+  std::stable_sort(v.begin(), v.end(), before);
+  size_t w = 0;
+  for (size_t i = 0; i < v.size(); ++i) {
+    if (i + 1 < v.size() && v[i + 1].first == v[i].first) continue;  // (the last of equal clients wins)
+    v[w++] = v[i];
+  }
+  v.resize(w);
   return true;
 }
 
@@ -189,7 +216,7 @@ enum Buf {
   B_TPRV, B_TMPRV, B_TMTAIL, B_TTREP, B_TOTAIL, B_THKEY, B_THVAL, B_TFLAG, B_TSCAN, B_SENT,
   B_OFIRST, B_OCIDX, B_OSIZE, B_OPOS, B_RSEG, B_RLEN, B_RSIZE, B_RPOS, B_OUT, B_SVOUT,
   B_VKMAP, B_VKREP, B_VKEYS, B_VNKEYS, B_VPOS, B_VD0, B_VN0, B_VD1, B_VN1, B_VORDER, B_VSEGS,
-  B_SCRATCH2, B_TMP2, B_CAPS, B_CLKEY, B_CLKEY2, B_CHKEY, B_CHVAL, B_CLDOC, B_DSFA, B_EMIT, B_DOCRNG, B_PACK, B_PACKPC, B_SPLITMETA, B_CLSINGLE, B_KSHARD, B_SOWNER, B_GFLAGS0, B_GFACC, B_LZBCLIENT,
+  B_SCRATCH2, B_TMP2, B_CAPS, B_CLKEY, B_CLKEY2, B_CHKEY, B_CHVAL, B_CLDOC, B_DSFA, B_EMIT, B_DOCRNG, B_PACK, B_PACKPC, B_SPLITMETA, B_CLSINGLE, B_KSHARD, B_SOWNER, B_GFLAGS0, B_GFACC, B_LZBCLIENT, B_SYNC, B_SYNCPLAN,
   B_COUNT
 };
 
@@ -2347,7 +2374,6 @@ int commit_merge(ycrdt_doc* d, const std::vector<ycrdt_buf>& extra, const ClockM
     e->before_final = nullptr;
   }
   b.pre_src = -1;
-  if (rc == YCRDT_OK) doc_marks(d);  // (the new state's decode, from this encode: queued on the stream)
   if (rc) {
     if (fresh && !d->spare.p) d->spare = nb;  // (kept for the next merge)
     else if (fresh) release_state(e, nb);
@@ -2379,6 +2405,9 @@ int commit_merge(ycrdt_doc* d, const std::vector<ycrdt_buf>& extra, const ClockM
   d->sv.swap(sv);
   d->last = e->last;
   d->view.valid = false;
+  // the new state's decode, from this encode (queued on the stream). Only now that the doc holds the
+  // state: a failure above leaves the doc its old state AND the marks that describe it
+  doc_marks(d);
   e->ws_owner = d;  // the workspace now holds this doc's merged store (ensure_view reuses it)
   // a doc that is read through its view (local ops, toJSON, get) takes the view now, while the
   // workspace holds its merge: another doc's merge in between would otherwise force a re-merge
@@ -2743,6 +2772,297 @@ int ycrdt_docs_states_packed(ycrdt_engine* e, ycrdt_doc* const* docs, size_t n, 
     else if (!d->state_len) { dst[o[2 * i]] = 0; dst[o[2 * i] + 1] = 0; }
     if (!d->sv.empty()) memcpy(dst + o[2 * i + 1], d->sv.data(), d->sv.size());
   }
+  return YCRDT_OK;
+}
+
+// Sync replies for many (document, peer state vector) pairs (crdt.js:286-291 batched over peers
+// and topics): planned and assembled from the documents' resident states (yc_sync.hip). Host
+// synchronisations of the device path: the size read-back and the copy-out.
+constexpr uint32_t SYNC_WALK_MAX = 65536;  // a mark-less state up to this many bytes is walked by one lane
+int ycrdt_docs_diff(ycrdt_engine* e, ycrdt_doc* const* docs, const ycrdt_buf* svs, size_t n, ycrdt_out* blob, uint64_t* offs,
+                    ycrdt_sync_stats* st) {
+  if (!e || !docs || !blob || !offs || (n && !svs)) return fail(YCRDT_E_ARG, "null arg");
+  for (size_t i = 0; i < n; ++i) {
+    if (!docs[i] || docs[i]->e != e) return fail(YCRDT_E_ARG, "document of another engine (or null) at " + std::to_string(i));
+    if (svs[i].len && !svs[i].ptr) return fail(YCRDT_E_ARG, "null state vector at " + std::to_string(i));
+  }
+  blob->ptr = nullptr;
+  blob->len = 0;
+  offs[0] = 0;
+  ycrdt_sync_stats S{};
+  S.walk_max = SYNC_WALK_MAX;
+  if (st) *st = S;
+  if (n == 0) {
+    blob->ptr = (uint8_t*)malloc(1);
+    if (!blob->ptr) return fail(YCRDT_E_CAPACITY, "host allocation failed");
+    return YCRDT_OK;
+  }
+  if (n >= 0x7FFFFFFFull) return fail(YCRDT_E_CAPACITY, "too many pairs");
+  // the peers' state vectors: clients ascending, one run per pair (as ycrdt_diff_updates uploads them)
+  std::vector<uint32_t> svk, svv;
+  std::vector<uint32_t> sv_off(n + 1, 0);
+  std::vector<std::pair<uint32_t, uint32_t>> one;
+  auto add_sv = [&](const std::vector<std::pair<uint32_t, uint32_t>>& v) {
+    for (const auto& kv : v) { svk.push_back(kv.first); svv.push_back(kv.second); }
+  };
+  for (size_t i = 0; i < n; ++i) {
+    one.clear();
+    if (svs[i].len && !parse_sv_sorted(svs[i].ptr, svs[i].len, one)) return fail(YCRDT_E_DECODE, "Integer out of range! (state vector)");
+    add_sv(one);
+    if (svk.size() >= 0xFFFFFFF0ull) return fail(YCRDT_E_CAPACITY, "state vectors too large");
+    sv_off[i + 1] = (uint32_t)svk.size();
+  }
+  HIPCHK(hipSetDevice(e->device));
+  {
+    std::vector<ycrdt_doc*> q;
+    for (size_t i = 0; i < n; ++i) if (!docs[i]->queue.empty()) q.push_back(docs[i]);
+    std::sort(q.begin(), q.end());
+    q.erase(std::unique(q.begin(), q.end()), q.end());
+    if (const int rc = flush_multi(e, q)) return rc;
+  }
+  // which path every pair takes
+  enum : uint8_t { K_SINGLE = 0, K_EMPTY, K_DEV };
+  const bool off = env_off("YCRDT_SYNC");
+  std::vector<uint8_t> kind(n, K_SINGLE);
+  auto marked = [](const ycrdt_doc* d) { return d->marks.p && d->marks_len == d->state_len && d->marks_cap > 0; };
+  size_t ndev = 0;
+  for (size_t i = 0; i < n; ++i) {
+    const ycrdt_doc* d = docs[i];
+    if (off || d->ing.has_pending || d->ing.has_ds || e->compat == 135) continue;
+    if (!d->state_len) { kind[i] = K_EMPTY; continue; }
+    if (d->state_len >= (size_t(1) << 31) || (!marked(d) && d->state_len > SYNC_WALK_MAX)) continue;
+    kind[i] = K_DEV;
+    ++ndev;
+  }
+  std::vector<std::vector<uint8_t>> host(n);  // replies of the pairs the device path does not answer
+  auto single = [&](size_t i) -> int {
+    ycrdt_out u{nullptr, 0};
+    if (const int rc = ycrdt_encode_state_as_update(docs[i], svs[i], &u)) return rc;
+    host[i].assign(u.ptr, u.ptr + u.len);
+    ycrdt_free(&u);
+    ++S.pairs_single;
+    return YCRDT_OK;
+  };
+  for (size_t i = 0; i < n; ++i) {
+    if (kind[i] == K_EMPTY) host[i] = {0, 0};
+    else if (kind[i] == K_SINGLE)
+      if (const int rc = single(i)) return rc;
+  }
+  std::vector<uint64_t> doffs;          // device replies: offsets in `dev`
+  std::vector<uint8_t> dev;
+  std::vector<size_t> dpair;            // device pair -> pair
+  if (ndev) {
+    auto& V = e->bufs;
+    g_bufs = &V;
+    hipStream_t s = e->stream;
+    // the documents named by the device pairs, each with its own state vector (the blocks' end clocks)
+    std::unordered_map<const ycrdt_doc*, uint32_t> dix;
+    std::vector<SyncDoc> hd;
+    std::vector<SyncWalk> hw;
+    std::vector<const ycrdt_doc*> dlist;
+    std::vector<SyncPair> hp;
+    uint64_t nitems = 0, walk_words = 0, walk_secs = 0;
+    for (size_t i = 0; i < n; ++i) {
+      if (kind[i] != K_DEV) continue;
+      const ycrdt_doc* d = docs[i];
+      auto it = dix.find(d);
+      if (it == dix.end()) {
+        std::vector<std::pair<uint32_t, uint32_t>> m;
+        if (!parse_sv_sorted(d->sv.data(), d->sv.size(), m)) return fail(YCRDT_E_DEVICE, "internal: a document's state vector does not parse");
+        SyncDoc D{};
+        D.state = (const uint8_t*)d->state.p;
+        D.state_len = (uint32_t)d->state_len;
+        D.sv_off = (uint32_t)svk.size();
+        D.sv_n = (uint32_t)m.size();
+        add_sv(m);
+        if (svk.size() >= 0xFFFFFFF0ull) return fail(YCRDT_E_CAPACITY, "state vectors too large");
+        if (marked(d)) {
+          const uint8_t* mk = (const uint8_t*)d->marks.p;
+          D.fbits = (const uint64_t*)mk;
+          D.secs = (const Section*)(mk + 16ull * d->marks_nw);
+          D.meta = (const uint32_t*)(mk + 16ull * d->marks_nw + sizeof(Section) * d->marks_cap);
+          D.nslots = d->marks_cap - 1;
+        } else {  // (pointers below, once the workspace is laid out)
+          D.nslots = (uint32_t)m.size();
+          hw.push_back(SyncWalk{(uint32_t)hd.size(), 0, nullptr, nullptr, nullptr});
+          walk_words += (d->state_len + 63) / 64;
+          walk_secs += D.nslots;
+        }
+        it = dix.emplace(d, (uint32_t)hd.size()).first;
+        hd.push_back(D);
+        dlist.push_back(d);
+      }
+      const SyncDoc& D = hd[it->second];
+      hp.push_back(SyncPair{it->second, sv_off[i], sv_off[i + 1] - sv_off[i], (uint32_t)nitems});
+      dpair.push_back(i);
+      nitems += D.nslots;
+      if (nitems >= 0x7FFFFFFFull) return fail(YCRDT_E_CAPACITY, "too many (pair, client block) items");
+      if (D.fbits) ++S.pairs_marks; else ++S.pairs_walk;
+    }
+    const uint32_t np = (uint32_t)hp.size(), nd = (uint32_t)hd.size(), nwk = (uint32_t)hw.size();
+    auto al = [](uint64_t x) { return (x + 63) & ~uint64_t(63); };
+    // device-only workspace: [counters | offsets | pair flags] (read back together), sizes, items, the walk's marks
+    const uint64_t o_ctr = 0, o_offs = 64, o_flag = o_offs + 8ull * (np + 1), rb_bytes = o_flag + 4ull * np;
+    const uint64_t o_psize = al(rb_bytes), o_ppc = al(o_psize + 4ull * (np + 1)), o_incl = al(o_ppc + 4ull * (np + 1));
+    const uint64_t o_items = al(o_incl + 4ull * np), o_wbits = al(o_items + sizeof(SyncItem) * nitems);
+    const uint64_t o_wsecs = al(o_wbits + 8 * walk_words), o_wmeta = al(o_wsecs + sizeof(Section) * walk_secs);
+    const uint64_t plan_bytes = o_wmeta + 16ull * nwk + 64;
+    // uploaded tables
+    const uint64_t u_docs = 0, u_walk = al(sizeof(SyncDoc) * (uint64_t)nd), u_pairs = al(u_walk + sizeof(SyncWalk) * (uint64_t)nwk);
+    const uint64_t u_svk = al(u_pairs + sizeof(SyncPair) * (uint64_t)np), u_svv = al(u_svk + 4ull * svk.size());
+    const uint64_t up_bytes = u_svv + 4ull * svk.size() + 64;
+    bool ok = true;
+    uint8_t* plan = take<uint8_t>(V, B_SYNCPLAN, plan_bytes, ok);
+    uint8_t* up = ok ? take<uint8_t>(V, B_SYNC, up_bytes, ok) : nullptr;
+    if (!ok) return fail(YCRDT_E_DEVICE, oom("sync replies"));
+    {
+      uint64_t wb = 0, wsx = 0;
+      for (uint32_t k = 0; k < nwk; ++k) {
+        SyncWalk& W = hw[k];
+        SyncDoc& D = hd[W.doc];
+        W.fbits = (uint64_t*)(plan + o_wbits) + wb;
+        W.secs = (Section*)(plan + o_wsecs) + wsx;
+        W.meta = (uint32_t*)(plan + o_wmeta) + 4ull * k;
+        D.fbits = W.fbits;
+        D.secs = W.secs;
+        D.meta = W.meta;
+        wb += (D.state_len + 63ull) / 64;
+        wsx += D.nslots;
+      }
+    }
+    std::vector<uint8_t> hup(up_bytes, 0);
+    memcpy(hup.data() + u_docs, hd.data(), sizeof(SyncDoc) * nd);
+    if (nwk) memcpy(hup.data() + u_walk, hw.data(), sizeof(SyncWalk) * nwk);
+    memcpy(hup.data() + u_pairs, hp.data(), sizeof(SyncPair) * np);
+    if (!svk.empty()) {
+      memcpy(hup.data() + u_svk, svk.data(), 4 * svk.size());
+      memcpy(hup.data() + u_svv, svv.data(), 4 * svv.size());
+    }
+    e->marks.clear();
+    e->phase_ms.clear();
+    HIPCHK(hipEventRecord(e->ev0, s));
+    mark(e, "sync_upload");
+    HIPCHK(hipMemcpyAsync(up, hup.data(), up_bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(plan, 0, rb_bytes, s));
+    if (walk_words) HIPCHK(hipMemsetAsync(plan + o_wbits, 0, 8 * walk_words, s));
+    SyncArgs A{};
+    A.docs = (const SyncDoc*)(up + u_docs);
+    A.pairs = (const SyncPair*)(up + u_pairs);
+    A.svk = (const uint32_t*)(up + u_svk);
+    A.svv = (const uint32_t*)(up + u_svv);
+    A.items = (SyncItem*)(plan + o_items);
+    A.psize = (uint32_t*)(plan + o_psize);
+    A.ppieces = (uint32_t*)(plan + o_ppc);
+    A.pincl = (uint32_t*)(plan + o_incl);
+    A.pflag = (uint32_t*)(plan + o_flag);
+    A.offs = (uint64_t*)(plan + o_offs);
+    A.ctr = (SyncCtr*)(plan + o_ctr);
+    A.np = np;
+    A.nitems = (uint32_t)nitems;
+    A.piece_max = PIECE_MAX;
+    A.dbg_bounds = getenv("YCRDT_DEBUG_BOUNDS") && getenv("YCRDT_DEBUG_BOUNDS")[0] == '1' ? 1u : 0u;
+    mark(e, "sync_walk");
+    launch_sync_walk(A.docs, (const SyncWalk*)(up + u_walk), nwk, A.ctr, A.dbg_bounds, s);
+    mark(e, "sync_plan");
+    launch_sync_plan(A, s);
+    mark(e, "sync_readback");
+    // the one size read-back: counters, offsets (the total is the last), pair flags
+    std::vector<uint8_t> rb(rb_bytes);
+    HIPCHK(hipMemcpyAsync(rb.data(), plan, rb_bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    const SyncCtr c = *(const SyncCtr*)(rb.data() + o_ctr);
+    if (c.err == ERR_CAPACITY && (c.err_info >> 16) == 0xB0DEu)
+      return fail(YCRDT_E_CAPACITY, "bounds check (YCRDT_DEBUG_BOUNDS): a position past its state at sync replies");
+    if (c.err == ERR_CAPACITY) return fail(YCRDT_E_CAPACITY, "a single sync reply over 4 GiB");
+    if (c.err) return map_err(c.err, "sync replies");
+    doffs.assign((const uint64_t*)(rb.data() + o_offs), (const uint64_t*)(rb.data() + o_offs) + np + 1);
+    const uint32_t* flags = (const uint32_t*)(rb.data() + o_flag);
+    const uint64_t total = doffs[np];
+    uint8_t* outb = take<uint8_t>(V, B_PACK, total + 16, ok);
+    Piece* dpc = ok ? take<Piece>(V, B_PACKPC, (size_t)c.npieces + 1, ok) : nullptr;
+    if (!ok) return fail(YCRDT_E_DEVICE, oom("sync replies"));
+    e->ws_owner = nullptr;  // B_PACK held a batch's split
+    mark(e, "sync_write");
+    launch_sync_write(A, outb, dpc, s);
+    mark(e, "sync_copy");
+    copy_pieces(dpc, c.npieces, s);
+    mark(e, "sync_d2h");
+    HIPCHK(hipEventRecord(e->ev1, s));
+    bool direct = ndev == n;  // every pair answered here: the blob is the device buffer's copy
+    for (uint32_t k = 0; k < np && direct; ++k) direct = flags[k] == 0;
+    uint8_t* dst = nullptr;
+    if (direct) {
+      dst = (uint8_t*)malloc(total ? total : 1);
+      if (!dst) return fail(YCRDT_E_CAPACITY, "host allocation failed");
+    } else {
+      dev.resize(total);
+      dst = dev.data();
+    }
+    // the copy-out (the counters of the write ride in front of it on the stream)
+    SyncCtr c2{};
+    int rc = hipMemcpyAsync(&c2, A.ctr, sizeof c2, hipMemcpyDeviceToHost, s) == hipSuccess ? YCRDT_OK : fail(YCRDT_E_DEVICE, "HIP error (sync replies)");
+    if (rc == YCRDT_OK) rc = d2h_span(e, dst, outb, total);
+    if (rc == YCRDT_OK && hipStreamSynchronize(s) != hipSuccess) rc = fail(YCRDT_E_DEVICE, "HIP error (sync replies)");
+    if (rc == YCRDT_OK && c2.err) rc = map_err(c2.err, "sync replies (write)");
+    if (rc) { if (direct) free(dst); return rc; }
+    mark(e, "end");
+    float ms = 0;
+    hipEventElapsedTime(&ms, e->ev0, e->ev1);
+    S.device_ms = ms;
+    S.cut_structs = c.cut_structs;
+    if (e->profiling) {
+      HIPCHK(hipStreamSynchronize(s));
+      for (size_t i = 0; i + 1 < e->marks.size(); ++i) {
+        float t = 0;
+        hipEventElapsedTime(&t, e->marks[i].second, e->marks[i + 1].second);
+        e->phase_ms.push_back({e->marks[i].first, (double)t});
+      }
+    }
+    if (direct) {
+      blob->ptr = dst;
+      blob->len = total;
+      memcpy(offs, doffs.data(), sizeof(uint64_t) * (n + 1));
+      S.out_bytes = total;
+      if (st) *st = S;
+      return YCRDT_OK;
+    }
+    // the pairs whose cut the slice helper refused: whatever the per-doc path gives
+    for (uint32_t k = 0; k < np; ++k)
+      if (flags[k]) {
+        if (marked(dlist[hp[k].doc])) --S.pairs_marks; else --S.pairs_walk;
+        kind[dpair[k]] = K_SINGLE;
+        if (const int rc2 = single(dpair[k])) return rc2;
+      }
+  }
+  uint64_t total = 0;
+  {
+    size_t k = 0;
+    for (size_t i = 0; i < n; ++i) {
+      offs[i] = total;
+      if (k < dpair.size() && dpair[k] == i) {
+        if (kind[i] == K_DEV) total += doffs[k + 1] - doffs[k]; else total += host[i].size();
+        ++k;
+      } else {
+        total += host[i].size();
+      }
+    }
+    offs[n] = total;
+  }
+  uint8_t* out = (uint8_t*)malloc(total ? total : 1);
+  if (!out) return fail(YCRDT_E_CAPACITY, "host allocation failed");
+  {
+    size_t k = 0;
+    for (size_t i = 0; i < n; ++i) {
+      const bool isdev = k < dpair.size() && dpair[k] == i;
+      if (isdev && kind[i] == K_DEV) memcpy(out + offs[i], dev.data() + doffs[k], doffs[k + 1] - doffs[k]);
+      else if (!host[i].empty()) memcpy(out + offs[i], host[i].data(), host[i].size());
+      if (isdev) ++k;
+    }
+  }
+  blob->ptr = out;
+  blob->len = total;
+  S.out_bytes = total;
+  if (st) *st = S;
   return YCRDT_OK;
 }
 

@@ -635,7 +635,7 @@ __device__ __attribute__((noinline)) uint32_t any_canon(const uint8_t* __restric
 // Inline and without printf: a call in a kernel (even one never taken) makes it keep registers
 // across the call — k_units 38 -> 60 VGPRs — and a Work reference passed out of line copies the
 // whole Work to scratch in every lane (k_units / k_seg_props 20 x slower; tests/test_kernel_resources.py)
-enum : uint32_t { BOUNDS_UNIT = 1, BOUNDS_KEY, BOUNDS_MERGE_SMALL, BOUNDS_ENCODE_SMALL, BOUNDS_OUTPUT, BOUNDS_DECODE_TAIL, BOUNDS_SECTIONS };
+enum : uint32_t { BOUNDS_UNIT = 1, BOUNDS_KEY, BOUNDS_MERGE_SMALL, BOUNDS_ENCODE_SMALL, BOUNDS_OUTPUT, BOUNDS_DECODE_TAIL, BOUNDS_SECTIONS, BOUNDS_SYNC };
 __device__ __forceinline__ void bounds_fail(Counters* ctr, uint32_t what) {
   raise_err(&ctr->err, ERR_CAPACITY);
   ctr->err_info = 0xB0DE0000u | what;

@@ -298,6 +298,14 @@ function encodeStateAsUpdate(doc, encodedTargetStateVector) {
   return binding.encodeStateAsUpdate(doc._h, encodedTargetStateVector);
 }
 
+// batch entry (not in Yjs): [Y.encodeStateAsUpdate(docs[i], svs[i]) for each pair] in one device
+// pass, answered from the docs' resident states — the sync responder of crdt.js:286-291 batched
+// over peers and topics. A doc may repeat; a null state vector asks for the full state.
+function encodeStatesAsUpdates(docs, svs) {
+  for (const d of docs) settle(d);
+  return binding.encodeStatesAsUpdates(docs.map((d) => d._h), svs);
+}
+
 function encodeStateVector(doc) {
   settle(doc);
   return binding.encodeStateVector(doc._h);
@@ -313,6 +321,7 @@ module.exports = {
   applyUpdatesMulti,
   encodeStateAsUpdate,
   encodeStateVector,
+  encodeStatesAsUpdates,
   mergeUpdates: (updates) => binding.mergeUpdates(updates),
   diffUpdate: (update, sv) => binding.diffUpdate(update, sv),
   // batch entry (not in Yjs): [Y.diffUpdate(u, sv) for each pair] in one device pass — the sync

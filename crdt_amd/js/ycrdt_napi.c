@@ -226,6 +226,67 @@ static napi_value js_encode_state_as_update(napi_env env, napi_callback_info inf
   return u8_from_out(env, &o);
 }
 
+/* encodeStatesAsUpdates(docs[], sv[]) → Uint8Array[]   (Y.encodeStateAsUpdate(docs[i], svs[i]) for
+ * every pair in one device pass, ycrdt_docs_diff: the sync responder of crdt.js:286-291 batched
+ * over peers and topics; a null / undefined state vector asks for the full state) */
+static napi_value js_encode_states_as_updates(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  bool a0 = false, a1 = false;
+  if (argc >= 2) { napi_is_array(env, argv[0], &a0); napi_is_array(env, argv[1], &a1); }
+  uint32_t n = 0, m = 0;
+  if (a0) napi_get_array_length(env, argv[0], &n);
+  if (a1) napi_get_array_length(env, argv[1], &m);
+  if (!a0 || !a1 || n != m) {
+    napi_throw_type_error(env, NULL, "encodeStatesAsUpdates(docs[], stateVectors[]) with one state vector per doc");
+    return NULL;
+  }
+  ycrdt_engine *e = engine(env);
+  if (!e) return NULL;
+  ycrdt_doc **docs = (ycrdt_doc **)calloc(n ? n : 1, sizeof(ycrdt_doc *));
+  ycrdt_buf *svs = (ycrdt_buf *)calloc(n ? n : 1, sizeof(ycrdt_buf));
+  uint64_t *offs = (uint64_t *)calloc((size_t)n + 1, sizeof(uint64_t));
+  if (!docs || !svs || !offs) {
+    free(docs); free(svs); free(offs);
+    napi_throw_error(env, NULL, "encodeStatesAsUpdates: out of host memory");
+    return NULL;
+  }
+  for (uint32_t i = 0; i < n; ++i) {
+    napi_value d, v;
+    napi_valuetype t;
+    napi_get_element(env, argv[0], i, &d);
+    napi_get_element(env, argv[1], i, &v);
+    napi_typeof(env, v, &t);
+    docs[i] = get_doc(env, d);
+    const int doc_ok = docs[i] != NULL;
+    if (!doc_ok || (t != napi_undefined && t != napi_null && !get_bytes(env, v, &svs[i]))) {
+      free(docs); free(svs); free(offs);
+      if (doc_ok) napi_throw_type_error(env, NULL, "state vectors must be Uint8Arrays");
+      return NULL;
+    }
+  }
+  ycrdt_out blob = {NULL, 0};
+  int rc = ycrdt_docs_diff(e, docs, svs, n, &blob, offs, NULL);
+  free(docs); free(svs);
+  if (rc != YCRDT_OK) { free(offs); return throw_rc(env, rc); }
+  napi_value arr = NULL;
+  if (napi_create_array_with_length(env, n, &arr) != napi_ok) arr = NULL;
+  for (uint32_t i = 0; arr && i < n; ++i) {
+    napi_value ab, ta;
+    void *data = NULL;
+    const size_t len = (size_t)(offs[i + 1] - offs[i]);
+    if (napi_create_arraybuffer(env, len, &data, &ab) != napi_ok ||
+        napi_create_typedarray(env, napi_uint8_array, len, ab, 0, &ta) != napi_ok) { arr = NULL; break; }
+    if (len) memcpy(data, blob.ptr + offs[i], len);
+    napi_set_element(env, arr, i, ta);
+  }
+  ycrdt_free(&blob);
+  free(offs);
+  if (!arr) napi_throw_error(env, NULL, "ycrdt: N-API call failed: encodeStatesAsUpdates result");
+  return arr;
+}
+
 /* encodeStateVector(doc)   (crdt.js:59,239,258,289) */
 static napi_value js_encode_state_vector(napi_env env, napi_callback_info info) {
   size_t argc = 1;
@@ -675,6 +736,7 @@ static napi_value init(napi_env env, napi_value exports) {
       {"mergeUpdates", NULL, js_merge_updates, NULL, NULL, NULL, napi_default, NULL},
       {"diffUpdate", NULL, js_diff_update, NULL, NULL, NULL, napi_default, NULL},
       {"diffUpdates", NULL, js_diff_updates, NULL, NULL, NULL, napi_default, NULL},
+      {"encodeStatesAsUpdates", NULL, js_encode_states_as_updates, NULL, NULL, NULL, napi_default, NULL},
       {"takeLocalUpdate", NULL, js_take_local_update, NULL, NULL, NULL, napi_default, NULL},
       {"trackLocalUpdates", NULL, js_track_local, NULL, NULL, NULL, napi_default, NULL},
       {"lastStats", NULL, js_last_stats, NULL, NULL, NULL, napi_default, NULL},

@@ -107,6 +107,29 @@ int ycrdt_apply_updates_multi(ycrdt_engine *e, ycrdt_doc *const *docs, const ycr
  * entries. dst == NULL only fills offs / total (size query). */
 int ycrdt_docs_states_packed(ycrdt_engine *e, ycrdt_doc *const *docs, size_t n, uint8_t *dst, uint64_t cap, uint64_t *offs,
                              uint64_t *total);
+/* Sync replies for many (document, peer state vector) pairs in one device pass: the responder of
+ * crdt.js:286-291 (`Y.encodeStateAsUpdate(y.doc, d.stateVector)` per joining or lagging peer)
+ * batched over peers and topics. Reply i = blob[offs[i] .. offs[i+1]) is byte-identical to
+ * ycrdt_encode_state_as_update(docs[i], svs[i]); offs holds n+1 entries; blob is released with
+ * ycrdt_free. svs[i].len == 0 means the full state. A doc may appear any number of times.
+ * A reply is planned from the document's resident state (which client blocks the peer lacks, which
+ * struct its clock cuts) and assembled from ranges of that state: no decode, no merge, no host
+ * round trip of the state (Sync replies). Documents with pending structs or a pending
+ * delete set, engines with compat 135, mark-less states over walk_max bytes and cuts the slice
+ * helper refuses take ycrdt_encode_state_as_update one by one (error included); YCRDT_SYNC=0 sends
+ * every pair there. Queued applies are flushed first (one batched merge). A state vector that does
+ * not parse fails the whole call with YCRDT_E_DECODE and no output. n == 0 needs no device. */
+typedef struct {
+  uint64_t pairs_marks;   /* answered from the doc's marks */
+  uint64_t pairs_walk;    /* mark-less state walked on the device */
+  uint64_t pairs_single;  /* went through ycrdt_encode_state_as_update, one by one */
+  uint64_t cut_structs;   /* structs re-encoded at an offset > 0 */
+  uint64_t out_bytes;
+  uint32_t walk_max;      /* largest mark-less state (bytes) the walk path takes */
+  double device_ms;
+} ycrdt_sync_stats;
+int ycrdt_docs_diff(ycrdt_engine *e, ycrdt_doc *const *docs, const ycrdt_buf *svs, size_t n,
+                    ycrdt_out *blob, uint64_t *offs, ycrdt_sync_stats *st /* may be NULL */);
 /* Runs the deferred applies now (every read does this implicitly). */
 int ycrdt_doc_flush(ycrdt_doc *d);
 /* Whether Yjs would hold pending structs (store.pendingStructs) / a pending delete set
