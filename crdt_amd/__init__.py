@@ -85,6 +85,21 @@ class SyncStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class JsonStats(ctypes.Structure):
+    _fields_ = [
+        ("pairs_device", ctypes.c_uint64),
+        ("pairs_single", ctypes.c_uint64),
+        ("pairs_empty", ctypes.c_uint64),
+        ("out_bytes", ctypes.c_uint64),
+        ("depth_max", ctypes.c_uint32),
+        ("name_max", ctypes.c_uint32),
+        ("device_ms", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 def library_path():
     # YCRDT_LIB: another build of the library (A/B experiments); the in-tree one by default
     return os.environ.get("YCRDT_LIB") or os.path.join(_HERE, "libycrdt.so")
@@ -105,7 +120,7 @@ EXPORTS = (
     "ycrdt_comm_unique_id", "ycrdt_comm_create", "ycrdt_comm_destroy", "ycrdt_batch_merge_sharded",
     "ycrdt_comm_sv_allreduce_max", "ycrdt_comm_ds_allgather", "ycrdt_comm_create_exchange", "ycrdt_route",
     "ycrdt_comm_fleet_sv_allreduce_max", "ycrdt_docs_states_packed", "ycrdt_comm_allgather", "ycrdt_device_count",
-    "ycrdt_docs_diff",
+    "ycrdt_docs_diff", "ycrdt_docs_json",
 )
 
 MERGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p)
@@ -185,6 +200,7 @@ def lib():
     L.ycrdt_docs_states_packed.argtypes = [vp, P(vp), sz, vp, ctypes.c_uint64, P(ctypes.c_uint64), P(ctypes.c_uint64)]
     L.ycrdt_route.argtypes = [ctypes.c_char_p, sz, u32]
     L.ycrdt_docs_diff.argtypes = [vp, P(vp), P(_Buf), sz, P(_Out), P(ctypes.c_uint64), P(SyncStats)]
+    L.ycrdt_docs_json.argtypes = [vp, P(vp), P(cs), P(i32), sz, P(_Out), P(ctypes.c_uint64), P(JsonStats)]
     L.ycrdt_route.restype = u32
     L.ycrdt_comm_fleet_sv_allreduce_max.argtypes = [vp, vp, P(u32), P(_Buf), sz, P(_Out), P(_Out), P(_Out)]
     L.ycrdt_map_size.argtypes = [vp, cs, cs, P(u32)]
@@ -774,6 +790,45 @@ def docs_diff_stats(docs, svs, engine=None):
         return [ctypes.string_at(out.ptr + o[i], o[i + 1] - o[i]) for i in range(len(docs))], st.as_dict()
     finally:
         lib().ycrdt_free(ctypes.byref(out))
+
+
+def docs_json_stats(docs, roots, kinds, engine=None):
+    """([d.root_json(root, kind) for d, root, kind in zip(docs, roots, kinds)], stats) in one device
+    pass (ycrdt_docs_json): the `c[key] = h[key].toJSON()` refresh of crdt.js:297-305 batched over
+    documents — one multi-document merge of the resident states, the view over it, and the JSON
+    text written on the device. kinds: "map" | "array" each (or one for all). A document may
+    repeat. stats: ycrdt_json_stats as a dict (which path the requests took)."""
+    import numpy as np
+
+    if isinstance(kinds, str):
+        kinds = [kinds] * len(docs)
+    if len(docs) != len(roots) or len(docs) != len(kinds):
+        raise ValueError("docs_json: one root and one kind per document")
+    for k in kinds:
+        if k not in ("map", "array"):
+            raise ValueError(f"docs_json: kind {k!r} (\"map\" | \"array\")")
+    n = len(docs)
+    eng = engine or (docs[0].engine if docs else default_engine())
+    hv = np.fromiter((d._h.value for d in docs), dtype=np.uint64, count=n) if n else np.zeros(1, np.uint64)
+    hs = hv.ctypes.data_as(ctypes.POINTER(ctypes.c_void_p))
+    names = (ctypes.c_char_p * max(n, 1))(*[r.encode() for r in roots])
+    ka = (ctypes.c_int * max(n, 1))(*[0 if k == "map" else 1 for k in kinds])
+    offs = np.zeros(n + 1, dtype=np.uint64)
+    out = _Out()
+    st = JsonStats()
+    _check(lib().ycrdt_docs_json(eng._h, hs, names, ka, n, ctypes.byref(out), offs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+                                 ctypes.byref(st)))
+    try:
+        o = offs.tolist()
+        blob = ctypes.string_at(out.ptr, out.len) if out.len else b""
+        return [blob[o[i]:o[i + 1]].decode() for i in range(n)], st.as_dict()
+    finally:
+        lib().ycrdt_free(ctypes.byref(out))
+
+
+def docs_json(docs, roots, kinds, engine=None) -> list:
+    """[d.root_json(root, kind) for d, root, kind in zip(docs, roots, kinds)] in one device pass (docs_json_stats)."""
+    return docs_json_stats(docs, roots, kinds, engine)[0]
 
 
 def docs_diff(docs, svs, engine=None) -> list:

@@ -20,6 +20,7 @@
 #include "yc_ingest.h"
 #include "yc_comm.h"
 #include "yc_sync.h"
+#include "yc_json.h"
 #include <thread>
 #include <atomic>
 #include "../../include/ycrdt.h"
@@ -216,7 +217,7 @@ enum Buf {
   B_TPRV, B_TMPRV, B_TMTAIL, B_TTREP, B_TOTAIL, B_THKEY, B_THVAL, B_TFLAG, B_TSCAN, B_SENT,
   B_OFIRST, B_OCIDX, B_OSIZE, B_OPOS, B_RSEG, B_RLEN, B_RSIZE, B_RPOS, B_OUT, B_SVOUT,
   B_VKMAP, B_VKREP, B_VKEYS, B_VNKEYS, B_VPOS, B_VD0, B_VN0, B_VD1, B_VN1, B_VORDER, B_VSEGS,
-  B_SCRATCH2, B_TMP2, B_CAPS, B_CLKEY, B_CLKEY2, B_CHKEY, B_CHVAL, B_CLDOC, B_DSFA, B_EMIT, B_DOCRNG, B_PACK, B_PACKPC, B_SPLITMETA, B_CLSINGLE, B_KSHARD, B_SOWNER, B_GFLAGS0, B_GFACC, B_LZBCLIENT, B_SYNC, B_SYNCPLAN,
+  B_SCRATCH2, B_TMP2, B_CAPS, B_CLKEY, B_CLKEY2, B_CHKEY, B_CHVAL, B_CLDOC, B_DSFA, B_EMIT, B_DOCRNG, B_PACK, B_PACKPC, B_SPLITMETA, B_CLSINGLE, B_KSHARD, B_SOWNER, B_GFLAGS0, B_GFACC, B_LZBCLIENT, B_SYNC, B_SYNCPLAN, B_JSON, B_JSONUP,
   B_COUNT
 };
 
@@ -3059,6 +3060,336 @@ int ycrdt_docs_diff(ycrdt_engine* e, ycrdt_doc* const* docs, const ycrdt_buf* sv
       if (isdev) ++k;
     }
   }
+  blob->ptr = out;
+  blob->len = total;
+  S.out_bytes = total;
+  if (st) *st = S;
+  return YCRDT_OK;
+}
+
+// ---- fleet toJSON (ycrdt_docs_json; yc_json.hip)
+namespace {
+
+struct JsonWant {            // one distinct (document, root, kind) of the device path
+  uint32_t doc;              // index among the call's device documents
+  std::string name;
+  int kind;
+  std::string text;
+  bool refused = false, done = false;
+};
+
+uint32_t json_name_hash(const std::string& s) {  // FNV-1a, as k_jsort_key hashes the root names
+  uint32_t h = 2166136261u;
+  for (unsigned char c : s) h = (h ^ c) * 16777619u;
+  return h;
+}
+
+// One device pass: the documents dl merged as one multi-document batch, the view over it, and the
+// text of the requests `ws` (indices into `wants`, their documents all in dl; pdoc maps a call
+// document to its index in dl). A request the device refuses — or every request, when the batch
+// cannot be viewed as one window or the merge fails — is left `refused` for the single path.
+int json_pass(ycrdt_engine* e, const std::vector<ycrdt_doc*>& dl, const std::vector<uint32_t>& pdoc,
+              std::vector<JsonWant>& wants, const std::vector<size_t>& ws, double& device_ms) {
+  auto refuse_all = [&]() { for (size_t k : ws) wants[k].refused = true; return YCRDT_OK; };
+  const uint32_t nd = (uint32_t)dl.size();
+  std::vector<Src> src;
+  std::vector<uint32_t> doc_of;
+  for (uint32_t j = 0; j < nd; ++j) { src.push_back(Src{(const uint8_t*)dl[j]->state.p, dl[j]->state_len, true}); doc_of.push_back(j); }
+  ycrdt_batch& b = scratch_batch(e);
+  b.jpasses = 0;
+  b.jstore.clear();
+  int rc = stage_srcs(&b, src, doc_of.data(), nd);
+  if (rc == YCRDT_OK && b.nwin > 1) { e->ws_owner = nullptr; return refuse_all(); }
+  if (rc == YCRDT_OK) rc = run_merge(e, &b, nullptr);
+  e->ws_owner = nullptr;  // the workspace holds many documents: a view re-merges its own
+  if (rc == YCRDT_E_DEVICE) return rc;
+  if (rc) return refuse_all();  // (the single path reports what is wrong with the document)
+  Work& w = e->w;
+  auto& V = e->bufs;
+  g_bufs = &V;
+  bool ok = true;
+  hipStream_t s = e->stream;
+  if (e->nlists == LISTS_UNNUMBERED) e->nlists = launch_ylists(w, e->nsegs, s);
+  const uint32_t nsegs = e->nsegs, nlists = e->nlists;
+  if (!nsegs) return refuse_all();
+  uint32_t narr = 0;
+  if (nlists) {
+    HIPCHK(hipMemcpyAsync(&narr, w.y_lstart + nlists, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+  }
+  ViewBufs vb;
+  const size_t ck = std::max<uint32_t>(w.cap_keys, 1);
+  vb.kmap = take<uint32_t>(V, B_VKMAP, ck, ok);
+  vb.krep = take<uint32_t>(V, B_VKREP, ck, ok);
+  vb.keys = take<ViewKey>(V, B_VKEYS, ck, ok);
+  vb.nkeys = take<uint32_t>(V, B_VNKEYS, 4, ok);
+  vb.pos_of = take<uint32_t>(V, B_VPOS, (size_t)nsegs + 1, ok);
+  vb.d0 = take<uint32_t>(V, B_VD0, (size_t)narr + 1, ok);
+  vb.n0 = take<uint32_t>(V, B_VN0, (size_t)narr + 1, ok);
+  vb.d1 = take<uint32_t>(V, B_VD1, (size_t)narr + 1, ok);
+  vb.n1 = take<uint32_t>(V, B_VN1, (size_t)narr + 1, ok);
+  vb.order = take<uint32_t>(V, B_VORDER, (size_t)narr + 1, ok);
+  vb.segs = take<ViewSeg>(V, B_VSEGS, (size_t)narr + 1, ok);
+  if (!ok) return fail(YCRDT_E_DEVICE, oom("view"));
+  if ((uint64_t)ck + narr >= 0x7FFFFFF0ull) return refuse_all();
+  // the requests, sorted by (document, root name hash), and their names
+  const uint32_t nreq = (uint32_t)ws.size();
+  std::vector<size_t> order(ws);
+  std::vector<JsonReq> reqs(nreq);
+  std::vector<uint8_t> names;
+  auto rkey = [&](size_t k) {
+    return (1ull << 63) | ((uint64_t)pdoc[wants[k].doc] << 32) | (json_name_hash(wants[k].name) >> 1);
+  };
+  std::sort(order.begin(), order.end(), [&](size_t x, size_t y) {
+    const uint64_t a = rkey(x), c = rkey(y);
+    return a != c ? a < c : x < y;
+  });
+  for (uint32_t r = 0; r < nreq; ++r) {
+    const JsonWant& q = wants[order[r]];
+    reqs[r] = JsonReq{rkey(order[r]), (uint32_t)names.size(), (uint32_t)q.name.size(), (uint32_t)q.kind, 0};
+    names.insert(names.end(), q.name.begin(), q.name.end());
+    if (names.size() >= 0xFFFFFFF0ull) return refuse_all();
+  }
+  // device workspace of the pass
+  const uint64_t n = (uint64_t)ck + narr;
+  uint64_t at = 0;
+  auto lay = [&](uint64_t bytes) { const uint64_t o = at; at = (at + bytes + 63) & ~uint64_t(63); return o; };
+  const uint64_t o_rb = lay(8ull * (nreq + 1) + 4ull * nreq);  // offsets | flags: read back together
+  const uint64_t o_roffs = o_rb, o_rflag = o_rb + 8ull * (nreq + 1);
+  const uint64_t o_rsize = lay(4ull * (nreq + 1));
+  const uint64_t o_orda = lay(4 * ck), o_ordb = lay(4 * ck), o_key = lay(8 * ck), o_gk = lay(8 * ck), o_inv = lay(4 * ck);
+  const uint64_t o_state = lay(4 * n), o_contrib = lay(4 * (n + 1)), o_tcontrib = lay(4ull * (narr + 1)), o_unres = lay(4 * (n + 1));
+  const uint64_t o_scanc = lay(8 * (n + 1)), o_scant = lay(8ull * (narr + 1)), o_scanu = lay(4 * (n + 1));
+  const uint64_t o_apos = lay(8 * n), o_cend = lay(8 * n), o_mbase = lay(8 * ck), o_abase = lay(8 * ck);
+  const uint64_t ws_bytes = at + 64;
+  at = 0;
+  const uint64_t u_reqs = lay(sizeof(JsonReq) * (uint64_t)nreq), u_names = lay(names.size());
+  const uint64_t up_bytes = at + 64;
+  uint8_t* W = take<uint8_t>(V, B_JSON, ws_bytes, ok);
+  uint8_t* U = ok ? take<uint8_t>(V, B_JSONUP, up_bytes, ok) : nullptr;
+  const size_t tmpb = prim_tmp_bytes(n + 2, ck + 2);
+  uint8_t* tmp = ok ? take<uint8_t>(V, B_TMP, tmpb, ok) : nullptr;
+  if (!ok) return fail(YCRDT_E_DEVICE, oom("fleet toJSON"));
+  std::vector<uint8_t> hup(up_bytes, 0);
+  memcpy(hup.data() + u_reqs, reqs.data(), sizeof(JsonReq) * nreq);
+  if (!names.empty()) memcpy(hup.data() + u_names, names.data(), names.size());
+  HIPCHK(hipEventRecord(e->ev0, s));
+  HIPCHK(hipMemcpyAsync(U, hup.data(), up_bytes, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemsetAsync(W + o_rb, 0, 8ull * (nreq + 1) + 4ull * nreq, s));
+  HIPCHK(hipMemsetAsync(W + o_apos, 0xFF, 8 * n, s));
+  HIPCHK(hipMemsetAsync(W + o_mbase, 0xFF, 8 * ck, s));
+  HIPCHK(hipMemsetAsync(W + o_abase, 0xFF, 8 * ck, s));
+  HIPCHK(hipMemsetAsync(W + o_inv, 0xFF, 4 * ck, s));
+  launch_view(w, vb, nsegs, nlists, narr, s);
+  JsonArgs A{};
+  A.bytes = (const uint8_t*)b.bytes.p;
+  A.nbytes = b.nbytes;
+  A.keys = vb.keys;
+  A.segs = vb.segs;
+  A.nkeys = vb.nkeys;
+  A.kmap = vb.kmap;
+  A.krep = vb.krep;
+  A.g_cidx = w.g_cidx;
+  A.cl_doc = b.ndocs > 1 ? w.cl_doc : nullptr;
+  A.y_lstart = w.y_lstart;
+  A.y_keys = w.y_keys;
+  A.ck = (uint32_t)ck;
+  A.narr = narr;
+  A.nlists = narr ? nlists : 0;
+  A.nreq = nreq;
+  A.ord = (uint32_t*)(W + o_orda);
+  A.gk = (uint64_t*)(W + o_gk);
+  A.inv = (uint32_t*)(W + o_inv);
+  A.state = (uint32_t*)(W + o_state);
+  A.contrib = (uint32_t*)(W + o_contrib);
+  A.tcontrib = (uint32_t*)(W + o_tcontrib);
+  A.unres = (uint32_t*)(W + o_unres);
+  A.scan_c = (uint64_t*)(W + o_scanc);
+  A.scan_t = (uint64_t*)(W + o_scant);
+  A.scan_u = (uint32_t*)(W + o_scanu);
+  A.apos = (uint64_t*)(W + o_apos);
+  A.cend = (uint64_t*)(W + o_cend);
+  A.mbase = (uint64_t*)(W + o_mbase);
+  A.abase = (uint64_t*)(W + o_abase);
+  A.reqs = (const JsonReq*)(U + u_reqs);
+  A.names = U + u_names;
+  A.rsize = (uint32_t*)(W + o_rsize);
+  A.rflag = (uint32_t*)(W + o_rflag);
+  A.roffs = (uint64_t*)(W + o_roffs);
+  // the keys in HostView::index's order: stable radix passes, least significant key first
+  static_assert(JSON_SORT_PASSES % 2 == 0, "the last pass writes A.ord");
+  {
+    uint32_t* in = A.ord;
+    uint32_t* out = (uint32_t*)(W + o_ordb);
+    for (uint32_t pass = 0; pass < JSON_SORT_PASSES; ++pass) {
+      launch_json_sort_key(A, pass, pass ? in : nullptr, (uint64_t*)(W + o_key), s);
+      sort_pairs_u64_u32(tmp, tmpb, (const uint64_t*)(W + o_key), A.gk, in, out, ck, s, 64);
+      std::swap(in, out);
+    }
+  }
+  launch_json_index(A, s);
+  // sweep 1 by level, a scan after each round (sweep 2 of that level)
+  for (uint32_t round = 0; round <= JSON_DEPTH_MAX; ++round) {
+    launch_json_size(A, round, s);
+    scan_u32_to_u64(tmp, tmpb, A.contrib, A.scan_c, n + 1, s);
+    scan_u32(tmp, tmpb, A.unres, A.scan_u, n + 1, s);
+    if (round == 0) scan_u32_to_u64(tmp, tmpb, A.tcontrib, A.scan_t, (uint64_t)narr + 1, s);
+  }
+  launch_json_requests(A, s);
+  scan_u32_to_u64(tmp, tmpb, A.rsize, A.roffs, (uint64_t)nreq + 1, s);
+  // the one size read-back: offsets (the total is the last), request flags, the view's counters
+  std::vector<uint8_t> rb(8ull * (nreq + 1) + 4ull * nreq);
+  Counters c;
+  uint32_t nkeys = 0;
+  HIPCHK(hipMemcpyAsync(rb.data(), W + o_rb, rb.size(), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(&c, w.ctr, sizeof(Counters), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(&nkeys, vb.nkeys, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (c.err || nkeys > ck) return refuse_all();
+  const uint64_t* roffs = (const uint64_t*)rb.data();
+  const uint32_t* rflag = (const uint32_t*)(rb.data() + 8ull * (nreq + 1));
+  const uint64_t total = roffs[nreq];
+  uint8_t* outb = take<uint8_t>(V, B_PACK, total + 64, ok);
+  if (!ok) return fail(YCRDT_E_DEVICE, oom("fleet toJSON text"));
+  A.out = outb;
+  A.out_cap = total;
+  // offsets top-down, one level per launch, then sweep 3
+  launch_json_roots(A, s);
+  for (uint32_t level = 0; level <= JSON_DEPTH_MAX; ++level) launch_json_place(A, s);
+  launch_json_write(A, s);
+  HIPCHK(hipEventRecord(e->ev1, s));
+  std::vector<uint8_t> text(total);
+  if (const int rc2 = d2h_span(e, text.data(), outb, total)) return rc2;
+  HIPCHK(hipStreamSynchronize(s));
+  float ms = 0;
+  hipEventElapsedTime(&ms, e->ev0, e->ev1);
+  device_ms += ms;
+  for (uint32_t r = 0; r < nreq; ++r) {
+    JsonWant& q = wants[order[r]];
+    if (rflag[r] || roffs[r + 1] - roffs[r] < 2) { q.refused = true; continue; }
+    q.text.assign((const char*)text.data() + roffs[r], roffs[r + 1] - roffs[r]);
+    q.done = true;
+  }
+  return YCRDT_OK;
+}
+
+}  // namespace
+
+constexpr uint64_t JSON_PASS_BYTES = uint64_t(1) << 31;  // resident state bytes merged per device pass (one 4 GiB window holds them)
+// (tests shrink a pass through YCRDT_DOCS_JSON_PASS_BYTES to run the several-pass path on a few documents)
+static uint64_t json_pass_bytes() {
+  const char* v = getenv("YCRDT_DOCS_JSON_PASS_BYTES");
+  const uint64_t x = v ? strtoull(v, nullptr, 10) : 0;
+  return x ? std::min(x, JSON_PASS_BYTES) : JSON_PASS_BYTES;
+}
+int ycrdt_docs_json(ycrdt_engine* e, ycrdt_doc* const* docs, const char* const* roots, const int* kinds, size_t n,
+                    ycrdt_out* blob, uint64_t* offs, ycrdt_json_stats* st) {
+  if (!e || !docs || !blob || !offs || (n && (!roots || !kinds))) return fail(YCRDT_E_ARG, "null arg");
+  for (size_t i = 0; i < n; ++i) {
+    if (!docs[i] || docs[i]->e != e) return fail(YCRDT_E_ARG, "document of another engine (or null) at " + std::to_string(i));
+    if (!roots[i]) return fail(YCRDT_E_ARG, "null root at " + std::to_string(i));
+    if (kinds[i] < 0 || kinds[i] > 1) return fail(YCRDT_E_ARG, "kind outside {0, 1} at " + std::to_string(i));
+  }
+  blob->ptr = nullptr;
+  blob->len = 0;
+  offs[0] = 0;
+  ycrdt_json_stats S{};
+  S.depth_max = JSON_DEPTH_MAX;
+  S.name_max = JSON_NAME_MAX;
+  if (st) *st = S;
+  if (n == 0) {
+    blob->ptr = (uint8_t*)malloc(1);
+    if (!blob->ptr) return fail(YCRDT_E_CAPACITY, "host allocation failed");
+    return YCRDT_OK;
+  }
+  if (n >= 0x7FFFFFFFull) return fail(YCRDT_E_CAPACITY, "too many requests");
+  HIPCHK(hipSetDevice(e->device));
+  {
+    std::vector<ycrdt_doc*> q;
+    for (size_t i = 0; i < n; ++i) if (!docs[i]->queue.empty()) q.push_back(docs[i]);
+    std::sort(q.begin(), q.end());
+    q.erase(std::unique(q.begin(), q.end()), q.end());
+    if (const int rc = flush_multi(e, q)) return rc;
+  }
+  // which path every request takes; the device path's distinct documents and triples
+  enum : uint8_t { K_SINGLE = 0, K_EMPTY, K_DEV };
+  const bool off = env_off("YCRDT_DOCS_JSON");
+  std::vector<uint8_t> kind(n, K_SINGLE);
+  std::vector<size_t> want_of(n, 0);
+  std::unordered_map<const ycrdt_doc*, uint32_t> dix;
+  std::vector<ycrdt_doc*> dlist;
+  std::vector<JsonWant> wants;
+  std::unordered_map<std::string, size_t> wix;
+  for (size_t i = 0; i < n; ++i) {
+    ycrdt_doc* d = docs[i];
+    if (off || d->ing.has_pending || d->ing.has_ds || e->compat == 135) continue;
+    if (!d->state_len) { kind[i] = K_EMPTY; continue; }
+    if (d->state_len >= JSON_PASS_BYTES) continue;
+    kind[i] = K_DEV;
+    auto it = dix.find(d);
+    if (it == dix.end()) { it = dix.emplace(d, (uint32_t)dlist.size()).first; dlist.push_back(d); }
+    std::string key((const char*)&it->second, 4);
+    key.push_back((char)kinds[i]);
+    key += roots[i];
+    auto wt = wix.find(key);
+    if (wt == wix.end()) {
+      wt = wix.emplace(key, wants.size()).first;
+      JsonWant q;
+      q.doc = it->second;
+      q.name = roots[i];
+      q.kind = kinds[i];
+      wants.push_back(std::move(q));
+    }
+    want_of[i] = wt->second;
+  }
+  // device passes: documents in call order, as many as one window holds
+  if (!wants.empty()) {
+    const uint64_t pass_bytes = json_pass_bytes();
+    std::vector<std::vector<size_t>> by_doc(dlist.size());
+    for (size_t k = 0; k < wants.size(); ++k) by_doc[wants[k].doc].push_back(k);
+    std::vector<uint32_t> pdoc(dlist.size(), 0);
+    size_t j = 0;
+    while (j < dlist.size()) {
+      std::vector<ycrdt_doc*> dl;
+      std::vector<size_t> ws;
+      uint64_t bytes = 0;
+      while (j < dlist.size() && (dl.empty() || bytes + dlist[j]->state_len + 64 <= pass_bytes)) {
+        bytes += (dlist[j]->state_len + 63) & ~size_t(63);
+        pdoc[j] = (uint32_t)dl.size();
+        dl.push_back(dlist[j]);
+        ws.insert(ws.end(), by_doc[j].begin(), by_doc[j].end());
+        ++j;
+      }
+      if (const int rc = json_pass(e, dl, pdoc, wants, ws, S.device_ms)) return rc;
+    }
+  }
+  // everything else one by one (a repeated triple once)
+  std::unordered_map<std::string, std::string> singles;
+  std::vector<const std::string*> text(n, nullptr);
+  static const std::string empty_map = "{}", empty_array = "[]";
+  for (size_t i = 0; i < n; ++i) {
+    if (kind[i] == K_EMPTY) { text[i] = kinds[i] == 0 ? &empty_map : &empty_array; ++S.pairs_empty; continue; }
+    if (kind[i] == K_DEV && wants[want_of[i]].done) { text[i] = &wants[want_of[i]].text; ++S.pairs_device; continue; }
+    const ycrdt_doc* d = docs[i];
+    std::string key((const char*)&d, sizeof d);
+    key.push_back((char)kinds[i]);
+    key += roots[i];
+    auto it = singles.find(key);
+    if (it == singles.end()) {
+      ycrdt_out o{nullptr, 0};
+      if (const int rc = ycrdt_doc_json(docs[i], roots[i], kinds[i], &o)) return rc;
+      it = singles.emplace(key, std::string((const char*)o.ptr, o.len)).first;
+      ycrdt_free(&o);
+    }
+    text[i] = &it->second;
+    ++S.pairs_single;
+  }
+  uint64_t total = 0;
+  for (size_t i = 0; i < n; ++i) { offs[i] = total; total += text[i]->size(); }
+  offs[n] = total;
+  uint8_t* out = (uint8_t*)malloc(total ? total : 1);
+  if (!out) return fail(YCRDT_E_CAPACITY, "host allocation failed");
+  for (size_t i = 0; i < n; ++i) memcpy(out + offs[i], text[i]->data(), text[i]->size());
   blob->ptr = out;
   blob->len = total;
   S.out_bytes = total;

@@ -1,0 +1,301 @@
+// yc_json.h — JSON.stringify text of lib0 `any` values, for the host and the device alike.
+//
+// any_json_text restates any_json of yc_host.cpp (lib0 readAny L0@1937 -> JSON.stringify) without
+// recursion and without allocation, so that the fleet toJSON kernels (yc_json.hip) write the same
+// bytes the host writer does: undefined members are dropped from objects and written null in
+// arrays, numbers take Number::toString's text (yc_num.h), float32 is widened, BigInt64 is its
+// signed decimal, a Uint8Array is {"0":b0,...}, strings are escaped as put_json_str does, object
+// members keep their encoded order. One function sizes (out == nullptr) and writes.
+#pragma once
+#include <cstdint>
+#include <cstring>
+
+#include "yc_parse.h"  // YC_HD, yc_num.h
+
+namespace yc {
+
+constexpr uint32_t ANY_JSON_DEPTH = 64;  // container levels of one `any` value the writer follows
+enum : uint32_t {
+  AJ_OK = 0,
+  AJ_UNDEF = 1,  // the value is `undefined`: nothing written (a map entry is omitted, an array member is null)
+  AJ_BAD = 2,    // truncated or not an `any` encoding
+  AJ_DEEP = 3,   // nested past ANY_JSON_DEPTH: the caller takes the host writer
+};
+
+struct JText {        // byte sink at position n; o == nullptr only counts; nothing is stored at or past cap
+  uint8_t* o;
+  uint64_t n;
+  uint64_t cap = ~0ull;
+  YC_HDI void ch(uint32_t c) {
+    if (o && n < cap) o[n] = (uint8_t)c;
+    ++n;
+  }
+  YC_HDI void lit(const char* s) {
+    for (; *s; ++s) ch((uint8_t)*s);
+  }
+  YC_HDI void raw(const uint8_t* s, uint64_t k) {
+    for (uint64_t i = 0; i < k; ++i) ch(s[i]);
+  }
+};
+
+YC_HD inline void json_put_esc(JText& o, const uint8_t* s, uint64_t n) {  // put_json_str (yc_host.cpp) without the quotes
+  for (uint64_t i = 0; i < n; ++i) {
+    const uint32_t c = s[i];
+    switch (c) {
+      case '"': o.ch('\\'); o.ch('"'); break;
+      case '\\': o.ch('\\'); o.ch('\\'); break;
+      case '\b': o.ch('\\'); o.ch('b'); break;
+      case '\f': o.ch('\\'); o.ch('f'); break;
+      case '\n': o.ch('\\'); o.ch('n'); break;
+      case '\r': o.ch('\\'); o.ch('r'); break;
+      case '\t': o.ch('\\'); o.ch('t'); break;
+      default:
+        if (c < 0x20) {
+          o.ch('\\'); o.ch('u'); o.ch('0'); o.ch('0');
+          o.ch(c >> 4 ? '1' : '0');
+          o.ch("0123456789abcdef"[c & 15u]);
+        } else {
+          o.ch(c);
+        }
+    }
+  }
+}
+YC_HD inline void json_put_str(JText& o, const uint8_t* s, uint64_t n) {
+  o.ch('"');
+  json_put_esc(o, s, n);
+  o.ch('"');
+}
+
+YC_HD inline void json_put_u64(JText& o, uint64_t v) {
+  char t[20];
+  uint32_t k = 0;
+  do { t[k++] = (char)('0' + v % 10); v /= 10; } while (v);
+  while (k) o.ch((uint8_t)t[--k]);
+}
+
+YC_HD inline void json_put_number(JText& o, double x) {  // JSON.stringify(Number)
+  uint64_t u;
+  memcpy(&u, &x, 8);
+  if (((u >> 52) & 0x7ffu) == 0x7ffu) { o.lit("null"); return; }  // NaN, +-Infinity
+  if (x == 0) { o.ch('0'); return; }
+  char d[20], t[40];
+  int32_t n;
+  const uint32_t k = f64_shortest(x < 0 ? -x : x, d, n);
+  const uint32_t len = num_text(x < 0, d, k, n, t);
+  o.raw((const uint8_t*)t, len);
+}
+
+YC_HD inline void json_put_bytes(JText& o, const uint8_t* p, uint64_t n) {  // JSON.stringify(Uint8Array)
+  o.ch('{');
+  for (uint64_t i = 0; i < n; ++i) {
+    if (i) o.ch(',');
+    o.ch('"');
+    json_put_u64(o, i);
+    o.ch('"');
+    o.ch(':');
+    json_put_u64(o, p[i]);
+  }
+  o.ch('}');
+}
+
+struct JRd {  // bounded reader over b[p, end): the lib0 0.2.42 forms of yc_host.cpp's Rd
+  const uint8_t* b;
+  uint64_t p, end;
+  bool ok;
+  YC_HDI uint32_t u8() {
+    if (p >= end) { ok = false; return 0; }
+    return b[p++];
+  }
+  YC_HD inline uint32_t vu() {
+    uint32_t v = 0, shift = 0;
+    for (;;) {
+      if (p >= end) { ok = false; return 0; }
+      const uint32_t r = b[p++];
+      if (shift < 32) v |= (r & 0x7fu) << shift;
+      shift += 7;
+      if (r < 0x80u) return v;
+      if (shift > 35) { ok = false; return 0; }
+    }
+  }
+  YC_HD inline double vi() {  // readVarInt: JS 32-bit shifts, `num >>> 0` on multi-byte values
+    uint32_t r = u8();
+    uint32_t num = r & 63u;
+    const double sign = (r & 64u) ? -1.0 : 1.0;
+    if (!(r & 128u)) return sign * (double)num;
+    uint32_t len = 6;
+    for (;;) {
+      r = u8();
+      if (!ok) return 0;
+      num |= (r & 127u) << (len & 31u);
+      len += 7;
+      if (r < 128u) return sign * (double)num;
+      if (len > 41) { ok = false; return 0; }
+    }
+  }
+  YC_HDI const uint8_t* take(uint64_t n) {
+    if (p > end || end - p < n) { ok = false; p = end; return b; }
+    const uint8_t* q = b + p;
+    p += n;
+    return q;
+  }
+};
+
+// One lib0 `any` value at b[p, end) as JSON text appended to `o`; p moves past the value. Iterative:
+// an explicit stack of (kind, remaining members, nothing written yet) per open container.
+YC_HD inline uint32_t any_json_text(const uint8_t* b, uint64_t& p, uint64_t end, JText& o) {
+  JRd r{b, p, end, true};
+  uint32_t rem[ANY_JSON_DEPTH];
+  uint64_t is_obj = 0, first = 0;  // one bit per level
+  uint32_t depth = 0;
+  for (;;) {
+    if (depth) {
+      const uint32_t t = depth - 1;
+      const uint64_t bit = 1ull << t;
+      if (rem[t] == 0) {
+        o.ch((is_obj & bit) ? '}' : ']');
+        if (--depth == 0) break;
+        continue;
+      }
+      --rem[t];
+      if (is_obj & bit) {
+        const uint32_t kl = r.vu();
+        const uint8_t* k = r.take(kl);
+        if (!r.ok) return AJ_BAD;
+        if (r.p < r.end && b[r.p] == 127) { ++r.p; continue; }  // an undefined member is dropped
+        if (!(first & bit)) o.ch(',');
+        first &= ~bit;
+        json_put_str(o, k, kl);
+        o.ch(':');
+      } else {
+        if (!(first & bit)) o.ch(',');
+        first &= ~bit;
+        if (r.p < r.end && b[r.p] == 127) { ++r.p; o.lit("null"); continue; }
+      }
+    }
+    const uint32_t tag = r.u8();
+    if (!r.ok) return AJ_BAD;
+    switch (tag) {
+      case 127: p = r.p; return AJ_UNDEF;  // (only at the top: members are handled above)
+      case 126: o.lit("null"); break;
+      case 125: { const double v = r.vi(); if (r.ok) json_put_number(o, v); break; }
+      case 124: {
+        const uint8_t* q = r.take(4);
+        if (!r.ok) break;
+        const uint32_t u = ((uint32_t)q[0] << 24) | ((uint32_t)q[1] << 16) | ((uint32_t)q[2] << 8) | q[3];
+        float f;
+        memcpy(&f, &u, 4);
+        json_put_number(o, (double)f);
+        break;
+      }
+      case 123: case 122: {
+        const uint8_t* q = r.take(8);
+        if (!r.ok) break;
+        uint64_t u = 0;
+        for (int i = 0; i < 8; ++i) u = (u << 8) | q[i];
+        if (tag == 123) {
+          double d;
+          memcpy(&d, &u, 8);
+          json_put_number(o, d);
+        } else {  // BigInt64: its signed decimal
+          if (u >> 63) { o.ch('-'); u = ~u + 1; }
+          json_put_u64(o, u);
+        }
+        break;
+      }
+      case 121: o.lit("false"); break;
+      case 120: o.lit("true"); break;
+      case 119: { const uint32_t n = r.vu(); const uint8_t* q = r.take(n); if (r.ok) json_put_str(o, q, n); break; }
+      case 116: { const uint32_t n = r.vu(); const uint8_t* q = r.take(n); if (r.ok) json_put_bytes(o, q, n); break; }
+      case 118: case 117: {
+        const uint32_t n = r.vu();
+        if (!r.ok) break;
+        if (depth == ANY_JSON_DEPTH) return AJ_DEEP;
+        rem[depth] = n;
+        const uint64_t bit = 1ull << depth;
+        first |= bit;
+        if (tag == 118) is_obj |= bit; else is_obj &= ~bit;
+        ++depth;
+        o.ch(tag == 118 ? '{' : '[');
+        continue;
+      }
+      default: return AJ_BAD;
+    }
+    if (!r.ok) return AJ_BAD;
+    if (depth == 0) break;
+  }
+  p = r.p;
+  return AJ_OK;
+}
+
+}  // namespace yc
+
+#if defined(__HIP__) || defined(__HIPCC__)
+// ---- fleet toJSON (ycrdt_docs_json): root JSON of many (document, root, kind) requests written on
+// the device over the view of ONE multi-document merge (yc_json.hip; DESIGN.md §Fleet toJSON).
+#include <hip/hip_runtime.h>
+
+#include "yc_view.h"
+
+namespace yc {
+
+constexpr uint32_t JSON_DEPTH_MAX = 4;   // nested-type levels below a root the device path follows
+constexpr uint32_t JSON_NAME_MAX = 64;   // longest map-entry name (bytes) the device ordering takes
+constexpr uint32_t JSON_SORT_PASSES = 2 + JSON_NAME_MAX / 8;  // (length, slot) | name chunks | group
+
+constexpr uint32_t JR_NAME = 1u;     // request flag: a root of another name shares its hash slot
+constexpr uint32_t JR_OPEN = 2u;     // ... something under the root is refused, malformed or nested too deep
+constexpr uint32_t JR_SIZE = 4u;     // ... its text would pass 4 GiB
+
+struct JsonReq {             // one distinct (document, root, kind), sorted by rkey
+  uint64_t rkey;             // root group key: 1 << 63 | document << 32 | name hash >> 1
+  uint32_t name_pos, name_len;  // in the uploaded name pool
+  uint32_t kind, pad;
+};
+
+// Items: [0, ck) the view keys in sorted order (a YMap entry each), [ck, ck + narr) the list segments.
+struct JsonArgs {
+  const uint8_t* bytes;      // the merged batch buffer the view's byte ranges point into
+  uint64_t nbytes;
+  const ViewKey* keys;
+  const ViewSeg* segs;
+  const uint32_t* nkeys;
+  const uint32_t* kmap;      // [ck] key slot -> view key
+  const uint32_t* krep;      // [ck] key slot -> a member segment
+  const uint32_t* g_cidx;    // segment -> client index
+  const uint32_t* cl_doc;    // client index -> document (nullptr: one document)
+  const uint32_t* y_lstart;  // [nlists + 1]
+  const uint32_t* y_keys;
+  uint32_t ck, narr, nlists, nreq;
+  uint32_t* ord;             // [ck] sorted position -> view key
+  uint64_t* gk;              // [ck] sorted group keys (parent unit | root key | ~0 past the keys)
+  uint32_t* inv;             // [ck] view key -> sorted position
+  uint32_t* state;           // [n] 0 open, 1 sized, 2 refused
+  uint32_t* contrib;         // [n + 1] bytes the item adds to its container, separator included
+  uint32_t* tcontrib;        // [narr + 1] ... to a YText (escaped, no quotes)
+  uint32_t* unres;           // [n + 1] 1: not sized
+  uint64_t* scan_c;          // [n + 1]
+  uint64_t* scan_t;          // [narr + 1]
+  uint32_t* scan_u;          // [n + 1]
+  uint64_t* apos;            // [n] where the item's text starts in the blob
+  uint64_t* cend;            // [n] where its container's closer stands (~0: a YText member)
+  uint64_t* mbase;           // [ck] group start -> position of the map's opener
+  uint64_t* abase;           // [ck] list key -> position of the list's opener (bit 63: a YText)
+  const JsonReq* reqs;
+  const uint8_t* names;
+  uint32_t* rsize;           // [nreq + 1]
+  uint32_t* rflag;           // [nreq]
+  uint64_t* roffs;           // [nreq + 1]
+  uint8_t* out;
+  uint64_t out_cap;
+};
+
+void launch_json_sort_key(const JsonArgs& a, uint32_t pass, const uint32_t* ord_in, uint64_t* key, hipStream_t s);
+void launch_json_index(const JsonArgs& a, hipStream_t s);          // inverse order, request names
+void launch_json_size(const JsonArgs& a, uint32_t round, hipStream_t s);
+void launch_json_requests(const JsonArgs& a, hipStream_t s);       // per-request sizes
+void launch_json_roots(const JsonArgs& a, hipStream_t s);          // root brackets, root container bases
+void launch_json_place(const JsonArgs& a, hipStream_t s);          // one level of positions, top-down
+void launch_json_write(const JsonArgs& a, hipStream_t s);
+
+}  // namespace yc
+#endif

@@ -1,0 +1,495 @@
+// yc_json.hip — fleet toJSON on gfx950: the JSON text of many (document, root, kind) requests,
+// written on the device over the view (yc_view.hip) of ONE multi-document merge. The host never
+// sees the state bytes or the view records; it gets the blob and the offsets (ycrdt_docs_json).
+//
+// Items are the view keys (a YMap entry each) in the host's order and the list segments in document
+// order, so that every container — a root map, a nested YMap, a YArray / YText list — is a
+// contiguous item range and its size is a difference of one exclusive scan:
+//   k_jsort_key   radix keys of the stable passes that order the keys by (container, entry name
+//                 bytes, name length, slot) — HostView::index's order
+//   k_jindex      inverse order; every root key checks the name of the requests that share its slot
+//   k_jsize       sweep 1, by level bottom-up: an item's bytes in its container (`"name":value,` /
+//                 `v,v,`); an item holding a nested type is sized once the scan of the round before
+//                 has sized all of the type's members (JSON_DEPTH_MAX + 1 rounds, a scan after each)
+//   k_jrequests   the size of every request (sweep 2: their exclusive scan gives the offsets)
+//   k_jroots      root brackets and the root containers' positions
+//   k_jplace      offsets top-down, one level per launch: an item placed in its container hands the
+//                 position of its nested type's opener to that type's container
+//   k_jwrite      sweep 3: every placed item writes its own bytes, all in parallel
+// Whatever the bounds refuse (entry names past JSON_NAME_MAX, types nested past JSON_DEPTH_MAX, an
+// `any` past ANY_JSON_DEPTH, malformed content) leaves its item unsized, which leaves every
+// container above it unsized: the request is flagged and the host answers it through ycrdt_doc_json.
+#include "yc_common.h"
+#include "yc_json.h"
+
+namespace yc {
+
+namespace {
+
+constexpr uint64_t NONE64 = ~0ull;
+constexpr uint64_t TEXT_BIT = 1ull << 63;
+enum : uint32_t { JS_OPEN = 0, JS_SIZED = 1, JS_REFUSED = 2 };
+enum : uint32_t { EM_OK = 0, EM_OMIT = 1, EM_PENDING = 2, EM_REFUSED = 3 };
+enum : uint32_t { R_JSON = 2, R_BINARY = 3, R_STRING = 4, R_EMBED = 5, R_FORMAT = 6, R_TYPE = 7, R_ANY = 8 };
+enum : uint32_t { BOX_MAP = 0, BOX_ARRAY = 1, BOX_TEXT = 2, BOX_XML = 3 };
+
+__device__ __forceinline__ uint64_t ld64(const uint64_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void st64(uint64_t* p, uint64_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+__device__ __forceinline__ uint32_t lower_bound_u64(const uint64_t* __restrict__ a, uint32_t n, uint64_t key) {
+  uint32_t lo = 0, hi = n;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (a[mid] < key) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+__device__ __forceinline__ uint32_t upper_bound_u64(const uint64_t* __restrict__ a, uint32_t n, uint64_t key) {
+  uint32_t lo = 0, hi = n;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (a[mid] <= key) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+__device__ __forceinline__ bool in_bytes(const JsonArgs& a, uint32_t pos, uint32_t len) { return (uint64_t)pos + len <= a.nbytes; }
+
+__device__ __forceinline__ uint32_t name_hash(const uint8_t* p, uint32_t n) {  // FNV-1a (the host hashes the requests alike)
+  uint32_t h = 2166136261u;
+  for (uint32_t i = 0; i < n; ++i) h = (h ^ p[i]) * 16777619u;
+  return h;
+}
+
+// the container a view key belongs to: its parent type item's unit, or (document, root name)
+__device__ __forceinline__ uint64_t group_key(const JsonArgs& a, const ViewKey& K) {
+  if (K.parent_unit != VNONE) return K.parent_unit;
+  const uint32_t r = K.slot < a.ck ? a.krep[K.slot] : VNONE;
+  if (r == VNONE || !in_bytes(a, K.name_pos, K.name_len)) return NONE64;
+  const uint32_t doc = a.cl_doc ? a.cl_doc[a.g_cidx[r]] : 0u;
+  return (1ull << 63) | ((uint64_t)(doc & 0x7FFFFFFFu) << 32) | (name_hash(a.bytes + K.name_pos, K.name_len) >> 1);
+}
+
+__global__ void k_jsort_key(JsonArgs a, uint32_t pass, const uint32_t* __restrict__ ord_in, uint64_t* __restrict__ key) {
+  const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= a.ck) return;
+  const uint32_t i = ord_in ? ord_in[p] : p;
+  if (pass == 0) a.ord[p] = p;  // (the first pass sorts the identity)
+  if (i >= *a.nkeys || i >= a.ck) { key[p] = NONE64; return; }
+  const ViewKey& K = a.keys[i];
+  const bool ps = (K.flags & VK_PSUB) && in_bytes(a, K.psub_pos, K.psub_len);
+  const uint32_t len = ps ? K.psub_len : 0u;
+  uint64_t k = 0;
+  if (pass == 0) {
+    k = ((uint64_t)len << 32) | K.slot;
+  } else if (pass <= JSON_NAME_MAX / 8) {  // name bytes [8c, 8c + 8), big-endian, zero padded: the last chunk first
+    const uint32_t c = JSON_NAME_MAX / 8 - pass;
+    for (uint32_t j = 0; j < 8; ++j) {
+      const uint32_t x = 8 * c + j;
+      k = (k << 8) | (x < len ? a.bytes[K.psub_pos + x] : 0u);
+    }
+  } else {
+    k = group_key(a, K);
+  }
+  key[p] = k;
+}
+
+__global__ void k_jindex(JsonArgs a) {
+  const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= a.ck) return;
+  const uint32_t i = a.ord[p];
+  if (i >= *a.nkeys || i >= a.ck) return;
+  a.inv[i] = p;
+  const uint64_t g = a.gk[p];
+  if (!(g >> 63) || g == NONE64) return;
+  // the requests of this document and name hash: each must name this root
+  const ViewKey& K = a.keys[i];
+  uint32_t lo = 0, hi = a.nreq;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (a.reqs[mid].rkey < g) lo = mid + 1; else hi = mid;
+  }
+  for (uint32_t r = lo; r < a.nreq && a.reqs[r].rkey == g; ++r) {
+    const JsonReq& q = a.reqs[r];
+    bool same = q.name_len == K.name_len;
+    for (uint32_t j = 0; same && j < K.name_len; ++j) same = a.names[q.name_pos + j] == a.bytes[K.name_pos + j];
+    if (!same) atomicOr(&a.rflag[r], JR_NAME);
+  }
+}
+
+// the first YArray / YText list among the keys [lo, hi) of one container (lists sort in front:
+// they carry no entry name)
+__device__ __forceinline__ uint32_t first_list(const JsonArgs& a, uint32_t lo, uint32_t hi) {
+  for (uint32_t p = lo; p < hi; ++p) {
+    const uint32_t i = a.ord[p];
+    if (i >= a.ck) return VNONE;
+    const ViewKey& K = a.keys[i];
+    if (!(K.flags & VK_PSUB)) return p;
+    if (K.psub_len) return VNONE;
+  }
+  return VNONE;
+}
+
+struct Box {                 // a nested type's text
+  uint64_t size;
+  uint32_t unres;            // members not sized
+  uint32_t mode;             // BOX_*
+  uint32_t lo;               // BOX_MAP: first key of its group (VNONE: no entry); else its list key (VNONE: no list)
+};
+
+__device__ __forceinline__ uint64_t boxed(uint64_t members) { return 2 + members - (members ? 1 : 0); }  // (every member ends in a separator)
+
+// segment items [x0, x1) of list key at sorted position kp
+__device__ __forceinline__ bool list_range(const JsonArgs& a, uint32_t kp, uint32_t& x0, uint32_t& x1) {
+  const uint32_t i = a.ord[kp];
+  if (i >= a.ck) return false;
+  const ViewKey& K = a.keys[i];
+  if ((uint64_t)K.seg0 + K.nseg > a.narr) return false;
+  x0 = K.seg0;
+  x1 = K.seg0 + K.nseg;
+  return true;
+}
+
+__device__ __forceinline__ Box type_box(const JsonArgs& a, uint32_t unit, uint32_t tr) {
+  Box b{2, 0, BOX_ARRAY, VNONE};
+  if (tr >= 3 && tr <= 6) { b.mode = BOX_XML; return b; }
+  const uint32_t lo = lower_bound_u64(a.gk, a.ck, unit), hi = upper_bound_u64(a.gk, a.ck, unit);
+  if (tr == 1) {
+    b.mode = BOX_MAP;
+    if (lo < hi) {
+      b.lo = lo;
+      b.size = boxed(a.scan_c[hi] - a.scan_c[lo]);
+      b.unres = a.scan_u[hi] - a.scan_u[lo];
+    }
+    return b;
+  }
+  b.mode = tr == 2 ? BOX_TEXT : BOX_ARRAY;
+  const uint32_t kp = first_list(a, lo, hi);
+  uint32_t x0 = 0, x1 = 0;
+  if (kp == VNONE) return b;
+  if (!list_range(a, kp, x0, x1)) { b.unres = 1; return b; }
+  b.lo = kp;
+  if (tr == 2) {
+    b.size = 2 + (a.scan_t[x1] - a.scan_t[x0]);
+  } else {
+    b.size = boxed(a.scan_c[a.ck + x1] - a.scan_c[a.ck + x0]);
+    b.unres = a.scan_u[a.ck + x1] - a.scan_u[a.ck + x0];
+  }
+  return b;
+}
+
+__device__ __forceinline__ uint32_t utf8_len(uint32_t c) { return c < 0x80u ? 1u : c < 0xE0u ? 2u : c < 0xF0u ? 3u : 4u; }
+
+// The elements of a visible view segment as JSON (seg_elements of yc_host.cpp). `entry`: a YMap
+// entry's value — its one element, nothing behind it, EM_OMIT when it is undefined; otherwise every
+// element followed by a separator, except the one that would stand where the container closes.
+__device__ __forceinline__ uint32_t emit_seg(const JsonArgs& a, const ViewSeg& s, bool entry, bool scans, JText& o, uint64_t cend) {
+  if (s.b0 > s.b1 || s.b1 > a.nbytes) return EM_REFUSED;
+  auto sep = [&]() {
+    if (!entry && (!o.o || o.n != cend)) o.ch(',');
+  };
+  JRd r{a.bytes, s.b0, s.b1, true};
+  const uint32_t n = entry ? 1u : s.len;
+  switch (s.ref) {
+    case R_ANY:
+      for (uint32_t i = 0; i < n; ++i) {
+        uint64_t p = r.p;
+        const uint32_t st = any_json_text(a.bytes, p, s.b1, o);
+        if (st == AJ_BAD || st == AJ_DEEP) return EM_REFUSED;
+        r.p = p;
+        if (st == AJ_UNDEF) {
+          if (entry) return EM_OMIT;
+          o.lit("null");
+        }
+        sep();
+      }
+      return EM_OK;
+    case R_JSON:
+      for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t k = r.vu();
+        const uint8_t* q = r.take(k);
+        if (!r.ok) return EM_REFUSED;
+        const char* u = "undefined";
+        bool undef = k == 9;
+        for (uint32_t j = 0; undef && j < 9; ++j) undef = q[j] == (uint8_t)u[j];
+        if (undef) {
+          if (entry) return EM_OMIT;
+          o.lit("null");
+        } else {
+          o.raw(q, k);
+        }
+        sep();
+      }
+      return EM_OK;
+    case R_STRING: {  // one element per character
+      uint64_t p = s.b0;
+      if (entry) {
+        if (p >= s.b1) return EM_OMIT;
+        uint64_t last = p;
+        while (p < s.b1) { last = p; p += utf8_len(a.bytes[p]); }
+        json_put_str(o, a.bytes + last, s.b1 - last);
+        return EM_OK;
+      }
+      while (p < s.b1) {
+        const uint64_t l = min((uint64_t)utf8_len(a.bytes[p]), s.b1 - p);
+        json_put_str(o, a.bytes + p, l);
+        sep();
+        p += l;
+      }
+      return EM_OK;
+    }
+    case R_BINARY: {
+      const uint32_t k = r.vu();
+      const uint8_t* q = r.take(k);
+      if (!r.ok) return EM_REFUSED;
+      json_put_bytes(o, q, k);
+      sep();
+      return EM_OK;
+    }
+    case R_EMBED: {
+      const uint32_t k = r.vu();
+      const uint8_t* q = r.take(k);
+      if (!r.ok) return EM_REFUSED;
+      o.raw(q, k);
+      sep();
+      return EM_OK;
+    }
+    case R_TYPE: {
+      const uint32_t tr = r.vu();
+      if (!r.ok) return EM_REFUSED;
+      if (!scans) return EM_PENDING;
+      const Box b = type_box(a, s.unit + s.len - 1, tr);
+      if (b.unres) return EM_PENDING;
+      if (o.o) {
+        const uint32_t open = b.mode == BOX_MAP ? '{' : b.mode == BOX_ARRAY ? '[' : '"';
+        const uint32_t close = b.mode == BOX_MAP ? '}' : b.mode == BOX_ARRAY ? ']' : '"';
+        JText c{o.o, o.n, o.cap};
+        c.ch(open);
+        c.n = o.n + b.size - 1;
+        c.ch(close);
+      }
+      o.n += b.size;
+      sep();
+      return EM_OK;
+    }
+    case R_FORMAT:
+      if (entry) return EM_OMIT;
+      return EM_OK;  // (not countable: never asked)
+    default:
+      o.lit("null");
+      sep();
+      return EM_OK;
+  }
+}
+
+__device__ __forceinline__ bool entry_live(const ViewKey& K) {
+  return (K.flags & VK_PSUB) && (K.win.flags & VS_SET) && !(K.win.flags & VS_DELETED) && (K.win.flags & VS_ITEM);
+}
+__device__ __forceinline__ bool member_live(const ViewSeg& s) {
+  return !(s.flags & VS_DELETED) && (s.flags & VS_COUNTABLE) && (s.flags & VS_ITEM);
+}
+
+// sweep 1, one level: sizes of the items still open
+__global__ void k_jsize(JsonArgs a, uint32_t round) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t n = a.ck + a.narr;
+  if (i > n) return;
+  if (i == n) { a.contrib[n] = 0; a.unres[n] = 0; a.tcontrib[a.narr] = 0; return; }
+  if (round && a.state[i] != JS_OPEN) return;
+  uint32_t st = JS_SIZED, bytes = 0;
+  JText o{nullptr, 0};
+  uint32_t em = EM_OMIT;
+  if (i < a.ck) {
+    const uint32_t ki = a.ord[i];
+    if (ki < *a.nkeys && ki < a.ck) {
+      const ViewKey& K = a.keys[ki];
+      if (entry_live(K)) {
+        if (K.psub_len > JSON_NAME_MAX || !in_bytes(a, K.psub_pos, K.psub_len)) {
+          em = EM_REFUSED;
+        } else {
+          json_put_str(o, a.bytes + K.psub_pos, K.psub_len);
+          o.ch(':');
+          em = emit_seg(a, K.win, true, round != 0, o, NONE64);
+          o.ch(',');
+        }
+      }
+    }
+  } else {
+    const ViewSeg& s = a.segs[i - a.ck];
+    if (round == 0) {  // what the segment adds to a YText: its escaped string, no quotes
+      uint32_t t = 0;
+      if (!(s.flags & VS_DELETED) && (s.flags & VS_ITEM) && s.ref == R_STRING && s.b0 <= s.b1 && s.b1 <= a.nbytes) {
+        JText q{nullptr, 0};
+        json_put_esc(q, a.bytes + s.b0, s.b1 - s.b0);
+        t = q.n > 0xFFFFFFF0ull ? 0u : (uint32_t)q.n;
+        if (q.n > 0xFFFFFFF0ull) em = EM_REFUSED;
+      }
+      a.tcontrib[i - a.ck] = t;
+    }
+    if (em != EM_REFUSED && member_live(s)) em = emit_seg(a, s, false, round != 0, o, NONE64);
+  }
+  if (em == EM_OK) {
+    if (o.n > 0xFFFFFFF0ull) st = JS_REFUSED; else bytes = (uint32_t)o.n;
+  } else if (em == EM_PENDING) {
+    st = JS_OPEN;
+  } else if (em == EM_REFUSED) {
+    st = JS_REFUSED;
+  }
+  a.state[i] = st;
+  a.contrib[i] = bytes;
+  a.unres[i] = st != JS_SIZED;
+}
+
+// the item range of a request's root container: keys [lo, hi) of its group (kind 0), or the
+// segments of the root's list (kind 1; kp = its key, VNONE: no such list)
+__device__ __forceinline__ void root_range(const JsonArgs& a, const JsonReq& q, uint32_t& lo, uint32_t& hi, uint32_t& kp) {
+  lo = lower_bound_u64(a.gk, a.ck, q.rkey);
+  hi = upper_bound_u64(a.gk, a.ck, q.rkey);
+  kp = VNONE;
+  if (q.kind == 0) return;
+  kp = first_list(a, lo, hi);
+  uint32_t x0 = 0, x1 = 0;
+  if (kp != VNONE && !list_range(a, kp, x0, x1)) kp = VNONE;
+  lo = a.ck + x0;
+  hi = a.ck + x1;
+}
+
+__global__ void k_jrequests(JsonArgs a) {
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r > a.nreq) return;
+  if (r == a.nreq) { a.rsize[r] = 0; return; }
+  a.rsize[r] = 0;
+  if (a.rflag[r]) return;
+  uint32_t lo, hi, kp;
+  root_range(a, a.reqs[r], lo, hi, kp);
+  if (a.scan_u[hi] - a.scan_u[lo]) { a.rflag[r] = JR_OPEN; return; }
+  const uint64_t size = boxed(a.scan_c[hi] - a.scan_c[lo]);
+  if (size > 0xFFFFFFF0ull) { a.rflag[r] = JR_SIZE; return; }
+  a.rsize[r] = (uint32_t)size;
+}
+
+__global__ void k_jroots(JsonArgs a) {
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= a.nreq || a.rflag[r]) return;
+  const JsonReq& q = a.reqs[r];
+  const uint64_t at = a.roffs[r], size = a.roffs[r + 1] - at;
+  if (size < 2 || at + size > a.out_cap) return;
+  a.out[at] = q.kind == 0 ? '{' : '[';
+  a.out[at + size - 1] = q.kind == 0 ? '}' : ']';
+  uint32_t lo, hi, kp;
+  root_range(a, q, lo, hi, kp);
+  if (q.kind == 0) {
+    if (lo < hi) st64(&a.mbase[lo], at);
+  } else if (kp != VNONE) {
+    st64(&a.abase[kp], at);
+  }
+}
+
+// the list key (sorted position) a segment item belongs to
+__device__ __forceinline__ uint32_t list_of_seg(const JsonArgs& a, uint32_t sp) {
+  if (!a.nlists) return VNONE;
+  uint32_t lo = 0, hi = a.nlists;  // last list l with y_lstart[l] <= sp
+  while (hi - lo > 1) { const uint32_t m = (lo + hi) >> 1; if (a.y_lstart[m] <= sp) lo = m; else hi = m; }
+  const uint32_t slot = a.y_keys[a.y_lstart[lo]];
+  if (slot >= a.ck) return VNONE;
+  const uint32_t ki = a.kmap[slot];
+  if (ki == VNONE || ki >= a.ck) return VNONE;
+  return a.inv[ki];
+}
+
+// offsets, one level: an item whose container has a position takes its own, and hands the position
+// of its nested type's opener on to that type's container
+__global__ void k_jplace(JsonArgs a) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t n = a.ck + a.narr;
+  if (i >= n || a.apos[i] != NONE64) return;
+  uint64_t at = NONE64, end = NONE64;
+  const ViewSeg* sg = nullptr;
+  uint64_t vpos = 0;
+  if (i < a.ck) {
+    if (!a.contrib[i]) return;
+    const uint64_t g = a.gk[i];
+    const uint32_t lo = lower_bound_u64(a.gk, a.ck, g), hi = upper_bound_u64(a.gk, a.ck, g);
+    const uint64_t base = ld64(&a.mbase[lo]);
+    if (base == NONE64) return;
+    at = base + 1 + (a.scan_c[i] - a.scan_c[lo]);
+    end = base + (a.scan_c[hi] - a.scan_c[lo]);  // = base + boxed(..) - 1
+    const ViewKey& K = a.keys[a.ord[i]];
+    sg = &K.win;
+    JText o{nullptr, 0};
+    json_put_str(o, a.bytes + K.psub_pos, K.psub_len);
+    vpos = at + o.n + 1;
+  } else {
+    const uint32_t sp = i - a.ck;
+    const uint32_t kp = list_of_seg(a, sp);
+    if (kp == VNONE || kp >= a.ck) return;
+    const uint64_t base = ld64(&a.abase[kp]);
+    if (base == NONE64) return;
+    uint32_t x0 = 0, x1 = 0;
+    if (!list_range(a, kp, x0, x1) || sp < x0 || sp >= x1) return;
+    if (base & TEXT_BIT) {
+      if (!a.tcontrib[sp]) return;
+      a.apos[i] = (base & ~TEXT_BIT) + 1 + (a.scan_t[sp] - a.scan_t[x0]);
+      a.cend[i] = NONE64;
+      return;
+    }
+    if (!a.contrib[i]) return;
+    at = base + 1 + (a.scan_c[i] - a.scan_c[a.ck + x0]);
+    end = base + (a.scan_c[a.ck + x1] - a.scan_c[a.ck + x0]);
+    sg = &a.segs[sp];
+    vpos = at;
+  }
+  a.cend[i] = end;
+  a.apos[i] = at;
+  if (sg->ref != R_TYPE) return;
+  JRd r{a.bytes, sg->b0, sg->b1, true};
+  const uint32_t tr = r.vu();
+  if (!r.ok) return;
+  const Box b = type_box(a, sg->unit + sg->len - 1, tr);
+  if (b.lo == VNONE || b.mode == BOX_XML) return;
+  if (b.mode == BOX_MAP) st64(&a.mbase[b.lo], vpos);
+  else st64(&a.abase[b.lo], vpos | (b.mode == BOX_TEXT ? TEXT_BIT : 0));
+}
+
+// sweep 3: every placed item writes its bytes
+__global__ void k_jwrite(JsonArgs a) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t n = a.ck + a.narr;
+  if (i >= n) return;
+  const uint64_t at = a.apos[i];
+  if (at == NONE64 || at >= a.out_cap) return;
+  const uint64_t end = a.cend[i];
+  JText o{a.out, at, a.out_cap};
+  if (i < a.ck) {
+    const ViewKey& K = a.keys[a.ord[i]];
+    json_put_str(o, a.bytes + K.psub_pos, K.psub_len);
+    o.ch(':');
+    emit_seg(a, K.win, true, true, o, end);
+    if (o.n != end) o.ch(',');
+    return;
+  }
+  const ViewSeg& s = a.segs[i - a.ck];
+  if (end == NONE64) {  // a YText member: the escaped string between the type's quotes
+    json_put_esc(o, a.bytes + s.b0, s.b1 - s.b0);
+    return;
+  }
+  emit_seg(a, s, false, true, o, end);
+}
+
+inline dim3 grid(uint64_t n) { return dim3((uint32_t)(n / 256 + 1)); }
+
+}  // namespace
+
+void launch_json_sort_key(const JsonArgs& a, uint32_t pass, const uint32_t* ord_in, uint64_t* key, hipStream_t s) {
+  hipLaunchKernelGGL(k_jsort_key, grid(a.ck), dim3(256), 0, s, a, pass, ord_in, key);
+}
+void launch_json_index(const JsonArgs& a, hipStream_t s) { hipLaunchKernelGGL(k_jindex, grid(a.ck), dim3(256), 0, s, a); }
+void launch_json_size(const JsonArgs& a, uint32_t round, hipStream_t s) {
+  hipLaunchKernelGGL(k_jsize, grid((uint64_t)a.ck + a.narr + 1), dim3(256), 0, s, a, round);
+}
+void launch_json_requests(const JsonArgs& a, hipStream_t s) { hipLaunchKernelGGL(k_jrequests, grid(a.nreq + 1), dim3(256), 0, s, a); }
+void launch_json_roots(const JsonArgs& a, hipStream_t s) { hipLaunchKernelGGL(k_jroots, grid(a.nreq), dim3(256), 0, s, a); }
+void launch_json_place(const JsonArgs& a, hipStream_t s) { hipLaunchKernelGGL(k_jplace, grid((uint64_t)a.ck + a.narr), dim3(256), 0, s, a); }
+void launch_json_write(const JsonArgs& a, hipStream_t s) { hipLaunchKernelGGL(k_jwrite, grid((uint64_t)a.ck + a.narr), dim3(256), 0, s, a); }
+
+}  // namespace yc

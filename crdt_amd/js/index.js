@@ -306,6 +306,22 @@ function encodeStatesAsUpdates(docs, svs) {
   return binding.encodeStatesAsUpdates(docs.map((d) => d._h), svs);
 }
 
+// batch entry (not in Yjs): [docs[i].getMap(names[i]).toJSON() / getArray(names[i]).toJSON() for
+// each request] in one device pass — the `c[key] = h[key].toJSON()` refresh of crdt.js:297-305 for
+// many documents after a fleet ingest. kinds: 'map' | 'array' each (or one for all). A doc may repeat.
+function rootsToJSON(docs, names, kinds) {
+  const ks = typeof kinds === 'string' ? docs.map(() => kinds) : kinds;
+  if (!Array.isArray(docs) || !Array.isArray(names) || !Array.isArray(ks) || docs.length !== names.length || docs.length !== ks.length) {
+    throw new TypeError('rootsToJSON(docs[], names[], kinds[]) with one name and one kind per doc');
+  }
+  const codes = ks.map((k) => {
+    if (k !== 'map' && k !== 'array') throw new TypeError("rootsToJSON: kind 'map' | 'array'");
+    return k === 'map' ? 0 : 1;
+  });
+  for (const d of docs) settle(d);
+  return binding.docsJson(docs.map((d) => d._h), names, codes).map((t) => JSON.parse(t));
+}
+
 function encodeStateVector(doc) {
   settle(doc);
   return binding.encodeStateVector(doc._h);
@@ -322,6 +338,7 @@ module.exports = {
   encodeStateAsUpdate,
   encodeStateVector,
   encodeStatesAsUpdates,
+  rootsToJSON,
   mergeUpdates: (updates) => binding.mergeUpdates(updates),
   diffUpdate: (update, sv) => binding.diffUpdate(update, sv),
   // batch entry (not in Yjs): [Y.diffUpdate(u, sv) for each pair] in one device pass — the sync

@@ -499,6 +499,68 @@ static napi_value js_doc_json(napi_env env, napi_callback_info info) {
   return s;
 }
 
+/* docsJson(docs[], roots[], kinds[]) → string[]   (docJson(docs[i], roots[i], kinds[i]) for every
+ * request in one device pass, ycrdt_docs_json: the `c[key] = h[key].toJSON()` refresh of
+ * crdt.js:297-305 batched over documents; kinds 0 = YMap, 1 = YArray) */
+static napi_value js_docs_json(napi_env env, napi_callback_info info) {
+  size_t argc = 3;
+  napi_value argv[3];
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  bool a0 = false, a1 = false, a2 = false;
+  if (argc >= 3) { napi_is_array(env, argv[0], &a0); napi_is_array(env, argv[1], &a1); napi_is_array(env, argv[2], &a2); }
+  uint32_t n = 0, m = 0, k = 0;
+  if (a0) napi_get_array_length(env, argv[0], &n);
+  if (a1) napi_get_array_length(env, argv[1], &m);
+  if (a2) napi_get_array_length(env, argv[2], &k);
+  if (!a0 || !a1 || !a2 || n != m || n != k) {
+    napi_throw_type_error(env, NULL, "docsJson(docs[], roots[], kinds[]) with one root and one kind per doc");
+    return NULL;
+  }
+  ycrdt_engine *e = engine(env);
+  if (!e) return NULL;
+  ycrdt_doc **docs = (ycrdt_doc **)calloc(n ? n : 1, sizeof(ycrdt_doc *));
+  char **roots = (char **)calloc(n ? n : 1, sizeof(char *));
+  int *kinds = (int *)calloc(n ? n : 1, sizeof(int));
+  uint64_t *offs = (uint64_t *)calloc((size_t)n + 1, sizeof(uint64_t));
+  int ok = docs && roots && kinds && offs;
+  if (!ok) napi_throw_error(env, NULL, "docsJson: out of host memory");
+  for (uint32_t i = 0; ok && i < n; ++i) {
+    napi_value d, r, q;
+    int32_t kind = 0;
+    napi_get_element(env, argv[0], i, &d);
+    napi_get_element(env, argv[1], i, &r);
+    napi_get_element(env, argv[2], i, &q);
+    docs[i] = get_doc(env, d);
+    if (!docs[i]) { ok = 0; break; }
+    if (!get_str(env, r, &roots[i], 0) || napi_get_value_int32(env, q, &kind) != napi_ok) {
+      napi_throw_type_error(env, NULL, "docsJson: roots must be strings, kinds 0 (map) or 1 (array)");
+      ok = 0;
+      break;
+    }
+    kinds[i] = kind;
+  }
+  ycrdt_out blob = {NULL, 0};
+  napi_value arr = NULL;
+  if (ok) {
+    int rc = ycrdt_docs_json(e, docs, (const char *const *)roots, kinds, n, &blob, offs, NULL);
+    if (rc != YCRDT_OK) {
+      throw_rc(env, rc);
+    } else {
+      if (napi_create_array_with_length(env, n, &arr) != napi_ok) arr = NULL;
+      for (uint32_t i = 0; arr && i < n; ++i) {
+        napi_value s;
+        if (napi_create_string_utf8(env, (const char *)blob.ptr + offs[i], (size_t)(offs[i + 1] - offs[i]), &s) != napi_ok) { arr = NULL; break; }
+        napi_set_element(env, arr, i, s);
+      }
+      ycrdt_free(&blob);
+      if (!arr) napi_throw_error(env, NULL, "ycrdt: N-API call failed: docsJson result");
+    }
+  }
+  if (roots) for (uint32_t i = 0; i < n; ++i) free(roots[i]);
+  free(docs); free(roots); free(kinds); free(offs);
+  return arr;
+}
+
 /* typeJson(doc, root, parentKey, kind) → toJSON of the root type (parentKey null) or of the YMap
  * (kind 0) / YArray (kind 1) stored under root[parentKey], reading that type's own list only */
 static napi_value js_type_json(napi_env env, napi_callback_info info) {
@@ -743,6 +805,7 @@ static napi_value init(napi_env env, napi_value exports) {
       {"version", NULL, js_version, NULL, NULL, NULL, napi_default, NULL},
       {"mapTypeAt", NULL, js_map_type_at, NULL, NULL, NULL, napi_default, NULL},
       {"docJson", NULL, js_doc_json, NULL, NULL, NULL, napi_default, NULL},
+      {"docsJson", NULL, js_docs_json, NULL, NULL, NULL, napi_default, NULL},
       {"typeJson", NULL, js_type_json, NULL, NULL, NULL, napi_default, NULL},
       {"mapEntries", NULL, js_map_entries, NULL, NULL, NULL, napi_default, NULL},
       {"mapSet", NULL, js_map_set, NULL, NULL, NULL, napi_default, NULL},

@@ -130,6 +130,32 @@ typedef struct {
 } ycrdt_sync_stats;
 int ycrdt_docs_diff(ycrdt_engine *e, ycrdt_doc *const *docs, const ycrdt_buf *svs, size_t n,
                     ycrdt_out *blob, uint64_t *offs, ycrdt_sync_stats *st /* may be NULL */);
+/* Root toJSON for many (document, root, kind) requests in one device pass: the `c[key] =
+ * h[key].toJSON()` refresh of crdt.js:297-305 batched over documents. Request i = blob[offs[i] ..
+ * offs[i+1]) is byte-identical to ycrdt_doc_json(docs[i], roots[i], kinds[i]) (kind 0 = map, 1 =
+ * array; a kind that does not match the root, or an absent root, gives {} / []); offs holds n+1
+ * entries; blob is released with ycrdt_free. A document may repeat, and so may a triple (it is
+ * computed once). The distinct documents' resident states are merged as ONE multi-document batch,
+ * the view kernels run over it, and the JSON text is sized, laid out and written on the device
+ * (Fleet toJSON): the host sees neither the state bytes nor the view records. Empty
+ * documents are answered inline. Documents with pending structs or a pending delete set, engines
+ * with compat 135, and whatever the device path's bounds refuse (shared types nested more than
+ * depth_max levels below the root, a map-entry name over name_max bytes, an `any` value nested
+ * past 64 levels, malformed content) take ycrdt_doc_json one by one (error included);
+ * YCRDT_DOCS_JSON=0 sends every request there. Queued applies are flushed first (one batched
+ * merge). pairs_device + pairs_single + pairs_empty == n. n == 0 needs no device. A null root, a
+ * kind outside {0, 1} or a document of another engine gives YCRDT_E_ARG and no output. */
+typedef struct {
+  uint64_t pairs_device;  /* text written on the device */
+  uint64_t pairs_single;  /* went through ycrdt_doc_json, one by one */
+  uint64_t pairs_empty;   /* empty document: "{}" / "[]", no device work */
+  uint64_t out_bytes;
+  uint32_t depth_max;     /* nested-type levels the device path takes (constant) */
+  uint32_t name_max;      /* longest map-entry name (bytes) the device ordering takes (constant) */
+  double device_ms;       /* view and JSON kernels of the passes (the merge before them not included) */
+} ycrdt_json_stats;
+int ycrdt_docs_json(ycrdt_engine *e, ycrdt_doc *const *docs, const char *const *roots, const int *kinds,
+                    size_t n, ycrdt_out *blob, uint64_t *offs, ycrdt_json_stats *st /* may be NULL */);
 /* Runs the deferred applies now (every read does this implicitly). */
 int ycrdt_doc_flush(ycrdt_doc *d);
 /* Whether Yjs would hold pending structs (store.pendingStructs) / a pending delete set
