@@ -2712,6 +2712,7 @@ void launch_struct_count(const Work& w, hipStream_t s) {
     hipLaunchKernelGGL(k_count_small, dim3(1), dim3(COUNT_LANES), 0, s, w.final_bits, w.wcnt, w.sec_bits, w.wsec, nwords);
     return;
   }
+  if (w.scan_fused && popc_scan2(w.final_bits, w.wcnt, w.sec_bits, w.wsec, nwords, s)) return;
   hipLaunchKernelGGL(k_popc, dim3(nwords / 256 + 1), dim3(256), 0, s, w.final_bits, w.scratch, nwords);
   scan_u32(w.tmp, w.tmp_bytes, w.scratch, w.wcnt, nwords + 1, s);
   hipLaunchKernelGGL(k_popc, dim3(nwords / 256 + 1), dim3(256), 0, s, w.sec_bits, w.scratch, nwords);
@@ -3671,13 +3672,152 @@ __global__ void k_struct_clock(Work w, uint32_t nstructs, uint32_t states) {
   if (i < nstructs) struct_clock_at(w, i, nstructs, states);
 }
 
+// Large batches: the same clocks without the length scan (an 8-byte column per struct, written
+// and read back only for two of its entries to be subtracted). A struct's END clock is a segmented
+// inclusive sum along the struct table — the section's first struct contributes the section clock
+// plus its length, every other struct its length — so one tiled pass makes it: a lane takes
+// SC_ITEMS consecutive structs (16-byte loads and stores, as k_scan_lb), sums them in registers,
+// the lanes' (sum after the last section start, has a start) pairs are scanned in the wavefront and
+// across the four wavefronts, and the tiles are chained by a decoupled look-back. A tile that holds
+// a section start knows its carry-out (the end clock of its last struct) without looking back: it
+// publishes that as inclusive at once and only fetches its own carry-in (lb_wave_lookback, closed).
+// The carry saturates at 2^33: past 2^32 only on invalid input, which raises ERR_DECODE at every
+// struct it reaches, as struct_clock_at does.
+constexpr uint32_t SC_ITEMS = 16, SC_TILE = 256 * SC_ITEMS;
+constexpr uint64_t SC_SAT = 1ull << 33;
+__global__ __launch_bounds__(256) void k_struct_clock_lb(Work w, uint32_t nstructs, uint32_t states, uint32_t vec, LbChains lb) {
+  __shared__ uint64_t wsum[4], wlen[4];
+  __shared__ uint32_t whead[4];
+  __shared__ uint64_t tile_pre;
+  const uint32_t tile = ordered_block_id(lb.ord, lb.ord_base);
+  const uint32_t t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const uint64_t base = (uint64_t)tile * SC_TILE + (uint64_t)t * SC_ITEMS;  // (< 2^32 + SC_TILE)
+  const bool full = vec && base + SC_ITEMS <= nstructs;
+  uint32_t sec[SC_ITEMS + 1], len[SC_ITEMS];
+  uint32_t info[SC_ITEMS + 1];
+  if (full) {
+#pragma unroll
+    for (uint32_t k = 0; k < SC_ITEMS / 4; ++k) {
+      const uint4 a = ((const uint4*)(w.s_sec + base))[k], b = ((const uint4*)(w.s_len + base))[k];
+      sec[4 * k] = a.x; sec[4 * k + 1] = a.y; sec[4 * k + 2] = a.z; sec[4 * k + 3] = a.w;
+      len[4 * k] = b.x; len[4 * k + 1] = b.y; len[4 * k + 2] = b.z; len[4 * k + 3] = b.w;
+    }
+    const uint4 q = *(const uint4*)(w.s_info + base);
+    const uint32_t qq[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+    for (uint32_t k = 0; k < SC_ITEMS; ++k) info[k] = (qq[k >> 2] >> (8 * (k & 3))) & 0xFFu;
+  } else {
+#pragma unroll
+    for (uint32_t k = 0; k < SC_ITEMS; ++k) {
+      const bool in = base + k < nstructs;
+      sec[k] = in ? w.s_sec[base + k] : NONE;
+      len[k] = in ? w.s_len[base + k] : 0u;
+      info[k] = in ? (uint32_t)w.s_info[base + k] : 0u;
+    }
+  }
+  // the neighbours: the struct before the lane's first (a section start is a change of s_sec) and
+  // the one after its last (the last struct of a run holds the client state)
+  const bool nxt = base + SC_ITEMS < nstructs;
+  sec[SC_ITEMS] = nxt ? w.s_sec[base + SC_ITEMS] : NONE;
+  info[SC_ITEMS] = nxt ? (uint32_t)w.s_info[base + SC_ITEMS] : 0u;
+  const uint32_t psec = base > 0 && base <= nstructs ? w.s_sec[base - 1] : NONE;
+  // the lane's run: end clocks relative to the lane's carry-in up to its first section start
+  uint64_t e[SC_ITEMS];
+  uint64_t run = 0, lsum = 0;
+  uint32_t heads = 0;
+#pragma unroll
+  for (uint32_t k = 0; k < SC_ITEMS; ++k) {
+    const bool in = base + k < nstructs;
+    const bool head = in && (base + k == 0 || sec[k] != (k ? sec[k - 1] : psec));
+    if (head) { run = w.sections[sec[k]].clock; heads |= 1u << k; }
+    run += len[k];
+    lsum += len[k];
+    e[k] = run;
+  }
+  // (sum after the last start, has a start) over the lanes before this one, and the tile's
+  uint64_t v = run;
+  uint32_t f = heads ? 1u : 0u;
+  for (uint32_t off = 1; off < 64; off <<= 1) {
+    const uint64_t pv = __shfl_up(v, off);
+    const uint32_t pf = __shfl_up(f, off);
+    if (lane >= off) { if (!f) v += pv; f |= pf; }
+  }
+  uint64_t ls = lsum;
+  for (uint32_t off = 32; off > 0; off >>= 1) ls += __shfl_xor(ls, off);
+  if (lane == 63) { wsum[wv] = v; whead[wv] = f; }
+  if (lane == 0) wlen[wv] = ls;
+  uint64_t cv = __shfl_up(v, 1);  // the lanes before this one in its wavefront
+  uint32_t cf = __shfl_up(f, 1);
+  if (lane == 0) { cv = 0; cf = 0; }
+  __syncthreads();
+  uint64_t tv = 0;  // the wavefronts before this one, then the whole tile
+  uint32_t tf = 0;
+#pragma unroll
+  for (uint32_t x = 0; x < 4; ++x) {
+    if (x == wv) {  // carry into this lane = (wavefronts before) then (lanes before)
+      if (!cf) cv += tv;
+      cf |= tf;
+    }
+    if (whead[x]) { tv = wsum[x]; tf = 1u; } else tv += wsum[x];
+  }
+  if (wv == 0) {
+    const uint64_t pre = lb_wave_lookback(lb.state, tile, lb.epoch, tv, tf != 0, SC_SAT);
+    if (lane == 0) {
+      tile_pre = pre < SC_SAT ? pre : SC_SAT;
+      // Σ input lengths (k_state_totals sums the shards): one atomic per tile, spread over words
+      if (states) atomicAdd(&w.ctr->in_len_sh[tile & (NSHARD - 1)], (unsigned long long)(wlen[0] + wlen[1] + wlen[2] + wlen[3]));
+    }
+  }
+  __syncthreads();
+  const uint64_t carry = cf ? cv : cv + tile_pre;
+  const uint32_t first = heads ? (uint32_t)__ffs((int)heads) - 1 : SC_ITEMS;  // the lane's structs before it take the carry
+  uint32_t clk[SC_ITEMS];
+  uint32_t bad = 0;  // structs whose end clock is past 2^32 (no clock written, as struct_clock_at)
+#pragma unroll
+  for (uint32_t k = 0; k < SC_ITEMS; ++k) {
+    const uint64_t endc = e[k] + (k < first ? carry : 0ull);
+    const bool in = base + k < nstructs;
+    const bool over = in && endc > 0xFFFFFFFFull;
+    bad |= (over ? 1u : 0u) << k;
+    clk[k] = (uint32_t)(endc - len[k]);
+    if (!in || over || !states) continue;
+    const uint32_t ref = info[k] & 31u;
+    if (ref == REF_SKIP) {  // rare: Skip lengths are subtracted from the item count
+      atomicAdd(&w.ctr->items, (unsigned long long)len[k]);
+      continue;
+    }
+    // clocks grow along a section: only the last non-skip struct of a run can hold the max
+    const bool last = base + k + 1 == nstructs || sec[k + 1] != sec[k] || (info[k + 1] & 31u) == REF_SKIP;
+    if (last) atomicMax(&w.cl_state[w.s_cidx[base + k]], (uint32_t)endc);
+  }
+  if (bad) raise_err(&w.ctr->err, ERR_DECODE);
+  if (full && !bad) {
+#pragma unroll
+    for (uint32_t k = 0; k < SC_ITEMS / 4; ++k)
+      ((uint4*)(w.s_clock + base))[k] = make_uint4(clk[4 * k], clk[4 * k + 1], clk[4 * k + 2], clk[4 * k + 3]);
+  } else {
+#pragma unroll
+    for (uint32_t k = 0; k < SC_ITEMS; ++k)
+      if (base + k < nstructs && !((bad >> k) & 1u)) w.s_clock[base + k] = clk[k];
+  }
+}
+// false: no look-back states could be allocated (the merge fails: s_lenscan does not exist here)
+static bool launch_struct_clock_lb(const Work& w, uint32_t nstructs, uint32_t states, hipStream_t s) {
+  const uint64_t tiles = ((uint64_t)nstructs + SC_TILE - 1) / SC_TILE;
+  LbChains lb;
+  if (!lb_launch(tiles, 1, s, lb)) return false;
+  const uint32_t vec = (((uintptr_t)w.s_sec | (uintptr_t)w.s_len | (uintptr_t)w.s_clock | (uintptr_t)w.s_info) & 15u) == 0;
+  hipLaunchKernelGGL(k_struct_clock_lb, dim3((uint32_t)tiles), dim3(256), 0, s, w, nstructs, states, vec, lb);
+  return true;
+}
+
 void launch_struct_decode(const Work& w, uint32_t nstructs, hipStream_t s) {
   if (!nstructs) return;
   hipLaunchKernelGGL(k_struct_decode, dim3((nstructs + 255) / 256), dim3(256), 0, s, w, nstructs);
   hipLaunchKernelGGL(k_struct_decode_deferred, dim3(std::min<uint32_t>(nstructs / 256 + 1, SD_DEFER_GRID)), dim3(256), 0, s, w);
 }
 void launch_struct_lenscan(const Work& w, uint32_t nstructs, hipStream_t s) {
-  if (nstructs) scan_u32_to_u64(w.tmp, w.tmp_bytes, w.s_len, w.s_lenscan, nstructs + 1, s);
+  if (nstructs && !clocks_fused(w, nstructs)) scan_u32_to_u64(w.tmp, w.tmp_bytes, w.s_len, w.s_lenscan, nstructs + 1, s);
 }
 
 // --------------------------------------------------------------------------- client states
@@ -3692,26 +3832,34 @@ __global__ void k_apply_caps(Work w) {
   const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c < w.ctr->nclients) apply_caps_at(w, c);
 }
-__global__ void k_state_totals(Work w, uint32_t nstructs) {  // U and Σ input lengths into the counters
+__global__ void k_state_totals(Work w, uint32_t nstructs, uint32_t fused) {  // U and Σ input lengths into the counters
   w.ctr->units = w.cl_base[w.ctr->nclients];
-  w.ctr->in_len = w.s_lenscan[nstructs];
+  if (!fused) { w.ctr->in_len = w.s_lenscan[nstructs]; return; }
+  unsigned long long n = 0;  // (k_struct_clock_lb's tile totals)
+  for (uint32_t k = 0; k < NSHARD; ++k) n += w.ctr->in_len_sh[k];
+  w.ctr->in_len = n;
 }
 // NC <= nsections: the states are zero past NC, so a scan over nsections + 1 entries gives cl_base
 // cl_state must be zero on entry (the caller's fill)
-void launch_struct_clocks(const Work& w, uint32_t nstructs, hipStream_t s) {  // lazy mode: clocks only
+bool launch_struct_clocks(const Work& w, uint32_t nstructs, hipStream_t s) {  // lazy mode: clocks only
+  if (clocks_fused(w, nstructs)) return launch_struct_clock_lb(w, nstructs, 0u, s);
   if (nstructs) hipLaunchKernelGGL(k_struct_clock, dim3((nstructs + 255) / 256), dim3(256), 0, s, w, nstructs, 0u);
+  return true;
 }
-void launch_states(const Work& w, uint32_t nstructs, uint32_t nsections, hipStream_t s) {
-  if (nstructs) hipLaunchKernelGGL(k_struct_clock, dim3((nstructs + 255) / 256), dim3(256), 0, s, w, nstructs, 1u);
+bool launch_states(const Work& w, uint32_t nstructs, uint32_t nsections, hipStream_t s) {
+  const bool fused = clocks_fused(w, nstructs);
+  if (fused) { if (!launch_struct_clock_lb(w, nstructs, 1u, s)) return false; }
+  else if (nstructs) hipLaunchKernelGGL(k_struct_clock, dim3((nstructs + 255) / 256), dim3(256), 0, s, w, nstructs, 1u);
   if (w.capped && nsections) hipLaunchKernelGGL(k_apply_caps, dim3(nsections / 256 + 1), dim3(256), 0, s, w);
   scan_u32_to_u64(w.tmp, w.tmp_bytes, w.cl_state, w.cl_base, nsections + 1, s);
-  hipLaunchKernelGGL(k_state_totals, dim3(1), dim3(1), 0, s, w, nstructs);
+  hipLaunchKernelGGL(k_state_totals, dim3(1), dim3(1), 0, s, w, nstructs, fused ? 1u : 0u);
+  return true;
 }
 
 // Small batches (integrate mode): the struct decode (rare contents inline, no deferred pass), the
 // clock-length scan, the clocks and client states, the caps, the state scan and the totals as
 // phases of ONE workgroup — one launch for six.
-constexpr uint32_t DT_LANES = 256, DT_SMALL = 4096;
+constexpr uint32_t DT_LANES = 256;  // (DT_SMALL structs: yc_work.h)
 __global__ __launch_bounds__(DT_LANES) void k_decode_tail_small(Work w, uint32_t nstructs, uint32_t nsections) {
   __shared__ __attribute__((aligned(16))) uint32_t win[DT_LANES * SD_STRIDE];
   __shared__ uint64_t part[DT_LANES];

@@ -1111,6 +1111,7 @@ int run_decode(ycrdt_engine* e, ycrdt_batch* b, bool lazy, Decoded& D, bool gene
                   {(uint32_t*)w.final_bits, (uint64_t)nwords * 2, 0u},
                   {(uint32_t*)w.sec_bits, (uint64_t)nwords * 2, 0u}}, s);
   w.dbg_bounds = getenv("YCRDT_DEBUG_BOUNDS") && getenv("YCRDT_DEBUG_BOUNDS")[0] == '1' ? 1u : 0u;
+  w.scan_fused = env_off("YCRDT_SCAN_FUSED") ? 0u : 1u;  // (read per merge: A/B in one process)
   w.upre = b->pre_src >= 0 && !b->pre_check ? b->pre_u : NONE;
   if (w.upre != NONE) launch_predecoded(w, b->pre_u, b->pre, false, s);  // (a doc state: its own encode's decode)
   const bool dbg_yata = getenv("YCRDT_DEBUG_YATA") && getenv("YCRDT_DEBUG_YATA")[0] == '1';
@@ -1195,7 +1196,8 @@ int run_decode(ycrdt_engine* e, ycrdt_batch* b, bool lazy, Decoded& D, bool gene
   w.s_win = b->nwin > 1 ? take<uint8_t>(V, B_SWIN, w.cap_structs, ok) : nullptr;
   w.s_sec = take<uint32_t>(V, B_SSEC, w.cap_structs, ok);
   w.s_len = take<uint32_t>(V, B_SLEN, w.cap_structs + 1, ok);
-  w.s_lenscan = take<uint64_t>(V, B_SLENSCAN, w.cap_structs + 1, ok);
+  // (8 B per struct, only where the length scan runs: the one-workgroup tail and YCRDT_SCAN_FUSED=0)
+  w.s_lenscan = quick || !clocks_fused(w, nstructs) ? take<uint64_t>(V, B_SLENSCAN, w.cap_structs + 1, ok) : nullptr;
   w.s_clock = take<uint32_t>(V, B_SCLOCK, w.cap_structs, ok);
   w.s_cidx = take<uint32_t>(V, B_SCIDX, w.cap_structs, ok);
   w.s_info = take<uint8_t>(V, B_SINFO, w.cap_structs, ok);
@@ -1296,10 +1298,10 @@ int run_decode(ycrdt_engine* e, ycrdt_batch* b, bool lazy, Decoded& D, bool gene
   launch_struct_lenscan(w, nstructs, s);
   if (!lazy) {
     fill_u32_multi({{w.cl_start, (uint64_t)nsections + 1, 0u}, {w.cl_state, (uint64_t)nsections + 1, 0u}}, s);
-    launch_states(w, nstructs, nsections, s);
+    if (!launch_states(w, nstructs, nsections, s)) return fail(YCRDT_E_DEVICE, oom("look-back states"));
   } else {
     HIPCHK(hipMemsetAsync(w.cl_start, 0, sizeof(uint32_t) * (nsections + 1), s));
-    launch_struct_clocks(w, nstructs, s);
+    if (!launch_struct_clocks(w, nstructs, s)) return fail(YCRDT_E_DEVICE, oom("look-back states"));
   }
   }
   HIPCHK(hipStreamWaitEvent(s, e->side_done, 0));

@@ -7,7 +7,8 @@
 //   k_ds_apply     delete-set application (readAndApplyDeleteSet, Y@11619) as unit flags
 //   k_refs         split points required by origin / rightOrigin references (getItemCleanEnd /
 //                  getItemCleanStart, Y@29100) + min child client per unit (list adjacency)
-//   k_cuts         struct boundaries -> bitmap; popcount scan -> segments
+//   k_segments_lb  struct boundaries -> bitmap, its popcount prefix and the segment starts in one
+//                  tiled look-back pass (k_cuts + scan + k_scatter_seg with YCRDT_SCAN_FUSED=0)
 //   k_seg_props    per-segment origin / rightOrigin / parent / flags; first pass of the YMap
 //                  winner reduction (plain stores of a child into its origin's slot)
 //   k_resolve      parent+parentSub resolution (Item.getMissing, Y@76507): climb the origin chain
@@ -349,10 +350,71 @@ void launch_units(const Work& w, uint32_t nstructs, uint32_t nclients, uint32_t 
   if (nx && w.ds_tails) hipLaunchKernelGGL(k_ds_tails, dim3(512), dim3(256), 0, s, w);
 }
 
+// Large batches: the cut words, their popcount prefix and the segment starts in one pass. A tile is
+// SG_ITEMS x 256 units, unit tile * SG_TILE + k * 256 + t lane t's k-th: the ballot of a wavefront
+// is the cut word of its 64 units, the tile's 64 words are prefixed in LDS (word k * 4 + wave: unit
+// order), the tiles by a decoupled look-back on the tile totals, and every lane with a cut stores
+// its unit at its segment number — consecutive lanes, consecutive segments: coalesced stores where
+// k_scatter_seg had one lane store the ~62 set bits of a dense word one by one. Neither the popcount
+// column nor a scan pass over it exists.
+constexpr uint32_t SG_ITEMS = 16, SG_TILE = 256 * SG_ITEMS, SG_WORDS = SG_TILE / 64;
+__global__ __launch_bounds__(256) void k_segments_lb(Work w, uint32_t nwords, uint64_t nunits, LbChains lb) {
+  __shared__ uint64_t cw[SG_WORDS];   // the tile's cut words
+  __shared__ uint32_t cp[SG_WORDS];   // cuts of the tile before each word
+  __shared__ uint32_t tile_pre;
+  const uint32_t tile = ordered_block_id(lb.ord, lb.ord_base);
+  const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const uint64_t g0 = (uint64_t)tile * SG_TILE;
+#pragma unroll 4
+  for (uint32_t k = 0; k < SG_ITEMS; ++k) {
+    const uint64_t word = __ballot(cut_at(w, g0 + k * 256 + threadIdx.x, nunits));
+    if (lane == 0) cw[k * 4 + wv] = word;
+  }
+  __syncthreads();
+  if (wv == 0) {  // (SG_WORDS = 64: a word per lane)
+    const uint64_t word = cw[lane];
+    const uint32_t c = (uint32_t)__popcll(word);
+    uint32_t inc = c;
+    for (uint32_t off = 1; off < 64; off <<= 1) {
+      const uint32_t y = __shfl_up(inc, off);
+      if (lane >= off) inc += y;
+    }
+    const uint32_t tot = __shfl(inc, 63);
+    const uint32_t pre = (uint32_t)lb_wave_lookback(lb.state, tile, lb.epoch, tot);
+    cp[lane] = inc - c;
+    if (lane == 0) tile_pre = pre;
+    const uint64_t wi = (uint64_t)tile * SG_WORDS + lane;
+    if (wi < nwords) {
+      w.u_cutbits[wi] = word;
+      w.u_wpre[wi] = pre + inc - c;
+    }
+    if (lane == 0 && g0 + SG_TILE >= nunits) {  // the tile of the last unit: the total and the sentinel
+      const uint32_t nsegs = pre + tot;
+      w.u_wpre[nwords] = nsegs;
+      w.g_start[nsegs] = (uint32_t)nunits;
+      w.ctr->nsegs = nsegs;
+    }
+  }
+  __syncthreads();
+  const uint32_t base = tile_pre;
+  const uint64_t lt = (1ull << lane) - 1ull;
+#pragma unroll 4
+  for (uint32_t k = 0; k < SG_ITEMS; ++k) {
+    const uint64_t word = cw[k * 4 + wv];
+    if ((word >> lane) & 1ull) w.g_start[base + cp[k * 4 + wv] + (uint32_t)__popcll(word & lt)] = (uint32_t)(g0 + k * 256 + threadIdx.x);
+  }
+}
+
 void launch_segments(const Work& w, uint32_t nclients, uint64_t nunits, hipStream_t s) {
   const uint32_t nwords = (uint32_t)((nunits + 63) / 64);
   if (nwords <= SEG_SMALL_WORDS) {
     hipLaunchKernelGGL(k_segments_small, dim3(1), dim3(SEG_LANES), 0, s, w, nunits);
+    return;
+  }
+  const uint64_t tiles = (nunits + SG_TILE - 1) / SG_TILE;  // (every tile publishes; the last holds unit U - 1)
+  LbChains lb;
+  if (w.scan_fused && lb_launch(tiles, 1, s, lb)) {
+    hipLaunchKernelGGL(k_segments_lb, dim3((uint32_t)tiles), dim3(256), 0, s, w, nwords, nunits, lb);
     return;
   }
   hipLaunchKernelGGL(k_cuts, dim3(nwords / 4 + 1), dim3(256), 0, s, w, nunits);

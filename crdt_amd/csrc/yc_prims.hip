@@ -243,6 +243,81 @@ bool ordered_ids(uint64_t nblocks, hipStream_t s, OrderedIds& out) {
   return true;
 }
 
+// The popcount prefixes of two bitmaps of nwords words (entries [0, nwords], the last the total) in
+// one launch: k_scan_lb's tile with the popcount taken as the words are loaded (no count column),
+// wavefront 0 looking back on the first bitmap's chain while wavefront 1 does on the second's.
+__global__ __launch_bounds__(LB_LANES) void k_popc_scan2(const uint64_t* __restrict__ b0, uint32_t* __restrict__ o0,
+                                                        const uint64_t* __restrict__ b1, uint32_t* __restrict__ o1, uint32_t nwords,
+                                                        uint32_t vec, LbChains lb) {
+  __shared__ uint32_t wtot[2][LB_LANES / 64];
+  __shared__ uint32_t tile_pre[2];
+  const uint32_t tile = ordered_block_id(lb.ord, lb.ord_base);
+  const uint32_t t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const uint64_t base = (uint64_t)tile * LB_TILE + (uint64_t)t * LB_ITEMS;
+  const bool full = vec && base + LB_ITEMS <= nwords;
+  uint32_t v[2][LB_ITEMS], sum[2], inc[2];
+#pragma unroll
+  for (uint32_t c = 0; c < 2; ++c) {
+    const uint64_t* __restrict__ bits = c ? b1 : b0;
+    if (full) {
+#pragma unroll
+      for (uint32_t k = 0; k < LB_ITEMS / 2; ++k) {
+        const ulonglong2 q = ((const ulonglong2*)(bits + base))[k];
+        v[c][2 * k] = (uint32_t)__popcll(q.x);
+        v[c][2 * k + 1] = (uint32_t)__popcll(q.y);
+      }
+    } else {
+#pragma unroll
+      for (uint32_t k = 0; k < LB_ITEMS; ++k) v[c][k] = base + k < nwords ? (uint32_t)__popcll(bits[base + k]) : 0u;
+    }
+    sum[c] = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < LB_ITEMS; ++k) sum[c] += v[c][k];
+    inc[c] = sum[c];
+    for (uint32_t off = 1; off < 64; off <<= 1) {
+      const uint32_t y = __shfl_up(inc[c], off);
+      if (lane >= off) inc[c] += y;
+    }
+    if (lane == 63) wtot[c][wv] = inc[c];
+  }
+  __syncthreads();
+  if (wv < 2) {
+    uint32_t agg = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < LB_LANES / 64; ++k) agg += wtot[wv][k];
+    const uint32_t pre = (uint32_t)lb_wave_lookback(lb.state + (wv ? lb.stride : 0), tile, lb.epoch, agg);
+    if (lane == 0) tile_pre[wv] = pre;
+  }
+  __syncthreads();
+#pragma unroll
+  for (uint32_t c = 0; c < 2; ++c) {
+    uint32_t* __restrict__ out = c ? o1 : o0;
+    uint32_t run = tile_pre[c] + inc[c] - sum[c];
+#pragma unroll
+    for (uint32_t k = 0; k < LB_LANES / 64; ++k) run += k < wv ? wtot[c][k] : 0u;
+    uint32_t o[LB_ITEMS];
+#pragma unroll
+    for (uint32_t k = 0; k < LB_ITEMS; ++k) { o[k] = run; run += v[c][k]; }
+    if (vec && base + LB_ITEMS <= (uint64_t)nwords + 1) {
+#pragma unroll
+      for (uint32_t k = 0; k < LB_ITEMS / 4; ++k)
+        ((uint4*)(out + base))[k] = make_uint4(o[4 * k], o[4 * k + 1], o[4 * k + 2], o[4 * k + 3]);
+    } else {
+#pragma unroll
+      for (uint32_t k = 0; k < LB_ITEMS; ++k)
+        if (base + k <= nwords) out[base + k] = o[k];
+    }
+  }
+}
+bool popc_scan2(const uint64_t* b0, uint32_t* o0, const uint64_t* b1, uint32_t* o1, uint32_t nwords, hipStream_t s) {
+  const uint64_t tiles = ((uint64_t)nwords + 1 + LB_TILE - 1) / LB_TILE;  // nwords + 1 entries
+  LbChains lb;
+  if (!lb_launch(tiles, 2, s, lb)) return false;
+  const uint32_t vec = (((uintptr_t)b0 | (uintptr_t)b1 | (uintptr_t)o0 | (uintptr_t)o1) & 15u) == 0;
+  hipLaunchKernelGGL(k_popc_scan2, dim3((uint32_t)tiles), dim3(LB_LANES), 0, s, b0, o0, b1, o1, nwords, vec, lb);
+  return true;
+}
+
 void scan_u32(void* tmp, size_t tmpb, const uint32_t* in, uint32_t* out, uint64_t n, hipStream_t s) {
   if (!n) return;
   if (n <= SMALL_SCAN_MAX) {

@@ -52,7 +52,8 @@ struct Counters {            // device-side counters, read back at the few host 
   unsigned long long ds_base;   // integrate encoder: byte position of the delete-set section
   unsigned long long items;  // Σ clock lengths of Skip structs (items = Σ all lengths − this)
   unsigned long long units;  // U = cl_base[NC] (copied on the device before a counter read)
-  unsigned long long in_len; // Σ input clock lengths = s_lenscan[S] (same)
+  unsigned long long in_len; // Σ input clock lengths (same)
+  unsigned long long in_len_sh[NSHARD];  // k_struct_clock_lb: its tiles' length totals, sharded by tile (summed into in_len)
 };
 
 struct DsRange {             // one decoded (client, clock, len) delete-set range
@@ -98,6 +99,8 @@ struct Work {
   const uint32_t* fwc_off = nullptr; // [nupd] record base of each record-mode update, NONE otherwise (null: none)
   uint32_t* rtab = nullptr;        // record mode: chain_len at every byte of those updates (k_rtab), indexed as fwc
   uint4* rk = nullptr;             // [nupd] record mode: the ranked last section (first struct, n, section, 1)
+  uint32_t scan_fused = 1;         // 0 (YCRDT_SCAN_FUSED=0, read per merge): the large batches' clocks, segment numbering
+                                   // and bitmap prefixes as separate column + scan passes (A/B, tests)
   uint32_t dbg_bounds = 0;         // YCRDT_DEBUG_BOUNDS=1: table indexes of the unit passes and the single-workgroup
                                    // kernels checked against their tables' sizes (bounds_fail: a message + ERR_CAPACITY)
   uint32_t fwc_walk = 256;         // k_fwc's walk bound (YCRDT_FWC_WALK; at FWM_WALK the walker never re-evaluates a chain-position header)
@@ -178,7 +181,7 @@ struct Work {
   uint8_t* s_win = nullptr;        // window of the struct's bytes (written only when nwin > 1)
   uint32_t* s_sec = nullptr;       // index into sections
   uint32_t* s_len = nullptr;
-  uint64_t* s_lenscan = nullptr;   // [S+1] exclusive prefix of s_len
+  uint64_t* s_lenscan = nullptr;   // [S+1] exclusive prefix of s_len (null where k_struct_clock_lb makes the clocks)
   uint32_t* s_clock = nullptr;
   uint32_t* s_cidx = nullptr;
   uint8_t* s_info = nullptr;
@@ -403,14 +406,20 @@ bool lb_launch(uint64_t tiles, uint32_t chains, hipStream_t s, LbChains& out);
 // spinning on its own predecessor) to the nearest inclusive prefix, publishes its own inclusive
 // prefix, and returns the tile-exclusive prefix (mod 2^40) in every lane. Tiles wait only on
 // lower ordered ids, which are running.
-__device__ __forceinline__ uint64_t lb_wave_lookback(unsigned long long* __restrict__ state, uint32_t tile, uint32_t epoch, uint64_t agg) {
+// closed: the tile knows its inclusive value without looking back (a segmented sum that restarts
+// inside the tile): `agg` is published at once as inclusive, the look-back only fetches the tile's
+// own carry-in and nothing is published a second time.
+// sat != 0: values saturate at `sat` (< 2^40) instead of wrapping (a sum only invalid input lets grow)
+__device__ __forceinline__ uint64_t lb_wave_lookback(unsigned long long* __restrict__ state, uint32_t tile, uint32_t epoch, uint64_t agg,
+                                                     bool closed = false, uint64_t sat = 0) {
   const uint32_t lane = threadIdx.x & 63;
   const unsigned long long ep = (unsigned long long)epoch << 42;
+  auto pack = [&](uint64_t v) -> unsigned long long { return sat ? (v < sat ? v : sat) : (v & LB_VAL); };
   if (tile == 0) {
-    if (lane == 0) __hip_atomic_store(&state[0], ep | (2ull << 40) | (agg & LB_VAL), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (lane == 0) __hip_atomic_store(&state[0], ep | (2ull << 40) | pack(agg), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     return 0;
   }
-  if (lane == 0) __hip_atomic_store(&state[tile], ep | (1ull << 40) | (agg & LB_VAL), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (lane == 0) __hip_atomic_store(&state[tile], ep | ((closed ? 2ull : 1ull) << 40) | pack(agg), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   uint64_t pre = 0;
   for (int64_t j = (int64_t)tile - 1;; j -= 64) {
     const int64_t me = j - (int64_t)lane;
@@ -430,7 +439,7 @@ __device__ __forceinline__ uint64_t lb_wave_lookback(unsigned long long* __restr
     pre += part;
     if (done) break;
   }
-  if (lane == 0) __hip_atomic_store(&state[tile], ep | (2ull << 40) | ((pre + agg) & LB_VAL), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (!closed && lane == 0) __hip_atomic_store(&state[tile], ep | (2ull << 40) | pack(pre + agg), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   return pre;
 }
 
@@ -726,6 +735,9 @@ bool wave_decode(const Work& w);                  // few small updates: k_wlen +
 void launch_client_hash(const Work& w, uint64_t* key, uint32_t* val, uint32_t mask, hipStream_t s);
 bool sections_small(const Work& w, uint32_t nsections, uint64_t* key, uint32_t* val, uint32_t mask, hipStream_t s);  // ranks + client table + hash, one workgroup
 void launch_struct_count(const Work& w, hipStream_t s);
+// wcnt / wsec: the popcount prefixes of two bitmaps of nwords words (nwords + 1 entries each) in one
+// look-back launch; false: no look-back states (the caller takes the separate passes)
+bool popc_scan2(const uint64_t* b0, uint32_t* o0, const uint64_t* b1, uint32_t* o1, uint32_t nwords, hipStream_t s);
 void launch_struct_scatter(const Work& w, hipStream_t s);
 void launch_ds_bound(const Work& w, hipStream_t s);
 bool count_ds_small(const Work& w, hipStream_t s);  // counts + delete-set bounds in one workgroup (small batches)
@@ -734,6 +746,9 @@ void launch_section_clients(const Work& w, uint32_t nsections, hipStream_t s);
 void launch_client_table(Work& w, uint32_t nsections, hipStream_t s);
 void launch_struct_decode(const Work& w, uint32_t nstructs, hipStream_t s);
 void launch_struct_lenscan(const Work& w, uint32_t nstructs, hipStream_t s);
+constexpr uint32_t DT_SMALL = 4096;  // structs of the one-workgroup decode tail (k_decode_tail_small)
+// the clocks without a length scan (k_struct_clock_lb): batches past DT_SMALL structs unless YCRDT_SCAN_FUSED=0
+inline bool clocks_fused(const Work& w, uint32_t nstructs) { return w.scan_fused && nstructs > DT_SMALL; }
 bool decode_tail_small(const Work& w, uint32_t nstructs, uint32_t nsections, hipStream_t s);
 void launch_decode_tail_small(const Work& w, uint32_t nstructs, uint32_t nsections, hipStream_t s);  // NONE: counts on the device  // one workgroup: structs .. client states (small, integrate)
 void launch_json_structs(const Work& w, uint32_t nstructs, hipStream_t s);  // JSON.parse of JSON-like contents
@@ -748,8 +763,9 @@ struct JItem {
 };
 void launch_json_canon(const Work& w, const uint32_t* list, uint32_t n, JItem* items, uint32_t* arena, uint32_t acap,
                        uint32_t lanes, const unsigned long long* offs, uint8_t* out, hipStream_t s);
-void launch_states(const Work& w, uint32_t nstructs, uint32_t nsections, hipStream_t s);  // clocks + client states
-void launch_struct_clocks(const Work& w, uint32_t nstructs, hipStream_t s);               // clocks only (lazy)
+// (false: clocks_fused and no look-back states — s_lenscan does not exist then)
+bool launch_states(const Work& w, uint32_t nstructs, uint32_t nsections, hipStream_t s);  // clocks + client states
+bool launch_struct_clocks(const Work& w, uint32_t nstructs, hipStream_t s);               // clocks only (lazy)
 
 void launch_units_fill(const Work& w, uint64_t nunits, hipStream_t s);
 void launch_units(const Work& w, uint32_t nstructs, uint32_t nclients, uint32_t nds, uint64_t nunits, bool ds_big, hipStream_t s);
