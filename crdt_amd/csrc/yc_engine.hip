@@ -3080,12 +3080,6 @@ struct JsonWant {            // one distinct (document, root, kind) of the devic
   bool refused = false, done = false;
 };
 
-uint32_t json_name_hash(const std::string& s) {  // FNV-1a, as k_jsort_key hashes the root names
-  uint32_t h = 2166136261u;
-  for (unsigned char c : s) h = (h ^ c) * 16777619u;
-  return h;
-}
-
 // One device pass: the documents dl merged as one multi-document batch, the view over it, and the
 // text of the requests `ws` (indices into `wants`, their documents all in dl; pdoc maps a call
 // document to its index in dl). A request the device refuses — or every request, when the batch
@@ -3140,7 +3134,7 @@ int json_pass(ycrdt_engine* e, const std::vector<ycrdt_doc*>& dl, const std::vec
   std::vector<JsonReq> reqs(nreq);
   std::vector<uint8_t> names;
   auto rkey = [&](size_t k) {
-    return (1ull << 63) | ((uint64_t)pdoc[wants[k].doc] << 32) | (json_name_hash(wants[k].name) >> 1);
+    return (1ull << 63) | ((uint64_t)pdoc[wants[k].doc] << 32) | (fnv_key((const uint8_t*)wants[k].name.data(), 0, (uint32_t)wants[k].name.size()) >> 1);  // as k_jsort_key hashes the root names
   };
   std::sort(order.begin(), order.end(), [&](size_t x, size_t y) {
     const uint64_t a = rkey(x), c = rkey(y);

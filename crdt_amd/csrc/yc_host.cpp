@@ -3,17 +3,18 @@
 // JSON follows Yjs 13.5.16 toJSON + JSON.stringify: YMap.toJSON (Y@51558, typeMapGetAll Y@49897:
 // the entry's item, skipped when deleted, value = last element of its content), YArray.toJSON
 // (typeListToArray Y@46408: every countable, undeleted element in list order), nested types
-// recurse; lib0 readAny (L0@1937) for ContentAny values, JSON.parse text for ContentJSON.
+// recurse; lib0 readAny (L0@1937) for ContentAny values, JSON.parse text for ContentJSON. The text
+// of every value and the walk over a segment's elements are yc_json.h's, the definitions the fleet
+// toJSON kernels (yc_json.hip) compile too; this file adds the containers around them, written
+// straight into the output string.
 // Local ops restate typeMapSet (Y@49334), typeMapDelete (Y@49261), typeListInsertGenerics
 // (Y@48365) + typeListInsertGenericsAfter (Y@47498) and typeListDelete (Y@48835): the new item's
 // origin / right origin are read off the view, and the struct is written as Item.write (Y@80416).
 #include "yc_host.h"
-#include "yc_parse.h"  // (yc_num.h: Number::toString for the JSON output)
+#include "yc_json.h"  // the value text: any_json_text and SegCursor, shared with the fleet toJSON kernels
 
 #include <algorithm>
 #include <array>
-#include <cmath>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 
@@ -23,170 +24,8 @@ namespace yc {
 
 namespace {
 
-enum : uint32_t {
-  R_GC = 0, R_DELETED = 1, R_JSON = 2, R_BINARY = 3, R_STRING = 4, R_EMBED = 5, R_FORMAT = 6, R_TYPE = 7,
-  R_ANY = 8, R_DOC = 9
-};
-
-struct Rd {
-  const uint8_t* b;
-  size_t p, end;
-  bool ok = true;
-  uint32_t u8() {
-    if (p >= end) { ok = false; return 0; }
-    return b[p++];
-  }
-  uint32_t vu() {  // lib0 0.2.42 readVarUint (32-bit accumulation)
-    uint32_t v = 0, shift = 0;
-    for (;;) {
-      if (p >= end) { ok = false; return 0; }
-      const uint32_t r = b[p++];
-      if (shift < 32) v |= (r & 0x7fu) << shift;
-      shift += 7;
-      if (r < 0x80u) return v;
-      if (shift > 35) { ok = false; return 0; }
-    }
-  }
-  double vi() {  // readVarInt: JS 32-bit shifts, `num >>> 0` on multi-byte values
-    uint32_t r = u8();
-    int32_t num = (int32_t)(r & 63u);
-    const double sign = (r & 64u) ? -1.0 : 1.0;
-    if (!(r & 128u)) return sign * num;
-    uint32_t len = 6;
-    for (;;) {
-      r = u8();
-      if (!ok) return 0;
-      num = num | (int32_t)((r & 127u) << (len & 31u));
-      len += 7;
-      if (r < 128u) return sign * (double)(uint32_t)num;
-      if (len > 41) { ok = false; return 0; }
-    }
-  }
-  const uint8_t* take(size_t n) {
-    if (end - p < n || p > end) { ok = false; p = end; return b; }
-    const uint8_t* q = b + p;
-    p += n;
-    return q;
-  }
-};
-
-void put_json_str(std::string& o, const uint8_t* s, size_t n) {
-  o.push_back('"');
-  for (size_t i = 0; i < n; ++i) {
-    const unsigned char c = s[i];
-    switch (c) {
-      case '"': o += "\\\""; break;
-      case '\\': o += "\\\\"; break;
-      case '\b': o += "\\b"; break;
-      case '\f': o += "\\f"; break;
-      case '\n': o += "\\n"; break;
-      case '\r': o += "\\r"; break;
-      case '\t': o += "\\t"; break;
-      default:
-        if (c < 0x20) {
-          char t[8];
-          snprintf(t, sizeof t, "\\u%04x", c);
-          o += t;
-        } else {
-          o.push_back((char)c);
-        }
-    }
-  }
-  o.push_back('"');
-}
-
-void put_number(std::string& o, double x) {  // JSON.stringify(Number): Number::toString's text (yc_num.h)
-  if (!std::isfinite(x)) { o += "null"; return; }
-  if (x == 0) { o += "0"; return; }
-  char d[20], t[40];
-  int32_t n;
-  const uint32_t k = f64_shortest(x < 0 ? -x : x, d, n);
-  o.append(t, num_text(x < 0, d, k, n, t));
-}
-
-double be_f64(const uint8_t* p) {
-  uint64_t u = 0;
-  for (int i = 0; i < 8; ++i) u = (u << 8) | p[i];
-  double d;
-  memcpy(&d, &u, 8);
-  return d;
-}
-float be_f32(const uint8_t* p) {
-  uint32_t u = 0;
-  for (int i = 0; i < 4; ++i) u = (u << 8) | p[i];
-  float f;
-  memcpy(&f, &u, 4);
-  return f;
-}
-
-void put_uint8array(std::string& o, const uint8_t* p, size_t n) {  // JSON.stringify(Uint8Array)
-  o.push_back('{');
-  for (size_t i = 0; i < n; ++i) {
-    char t[32];
-    snprintf(t, sizeof t, "%s\"%zu\":%u", i ? "," : "", i, p[i]);
-    o += t;
-  }
-  o.push_back('}');
-}
-
-// lib0 readAny -> JSON text; returns false for `undefined` (the caller omits / nulls it)
-bool any_json(Rd& r, std::string& o, int depth) {
-  if (depth > 4000) { r.ok = false; return false; }  // lib0 readAny recurses without a limit (V8 overflows its stack near here)
-  const uint32_t tag = r.u8();
-  switch (tag) {
-    case 127: return false;  // undefined
-    case 126: o += "null"; return true;
-    case 125: put_number(o, r.vi()); return true;
-    case 124: { const uint8_t* q = r.take(4); if (r.ok) put_number(o, (double)be_f32(q)); return true; }
-    case 123: { const uint8_t* q = r.take(8); if (r.ok) put_number(o, be_f64(q)); return true; }
-    case 122: {  // BigInt64 (JSON.stringify would throw; written as its decimal value)
-      const uint8_t* q = r.take(8);
-      if (!r.ok) return true;
-      uint64_t u = 0;
-      for (int i = 0; i < 8; ++i) u = (u << 8) | q[i];
-      o += std::to_string((long long)u);
-      return true;
-    }
-    case 121: o += "false"; return true;
-    case 120: o += "true"; return true;
-    case 119: { const uint32_t n = r.vu(); const uint8_t* q = r.take(n); if (r.ok) put_json_str(o, q, n); return true; }
-    case 118: {
-      const uint32_t n = r.vu();
-      o.push_back('{');
-      bool first = true;
-      for (uint32_t i = 0; i < n && r.ok; ++i) {
-        const uint32_t kl = r.vu();
-        const uint8_t* k = r.take(kl);
-        std::string v;
-        if (!any_json(r, v, depth + 1)) continue;  // undefined members are dropped
-        if (!first) o.push_back(',');
-        first = false;
-        put_json_str(o, k, kl);
-        o.push_back(':');
-        o += v;
-      }
-      o.push_back('}');
-      return true;
-    }
-    case 117: {
-      const uint32_t n = r.vu();
-      o.push_back('[');
-      for (uint32_t i = 0; i < n && r.ok; ++i) {
-        if (i) o.push_back(',');
-        std::string v;
-        if (any_json(r, v, depth + 1)) o += v;
-        else o += "null";
-      }
-      o.push_back(']');
-      return true;
-    }
-    case 116: { const uint32_t n = r.vu(); const uint8_t* q = r.take(n); if (r.ok) put_uint8array(o, q, n); return true; }
-    default: r.ok = false; return false;
-  }
-}
-
-bool skip_any(Rd& r, int depth) {
-  if (depth > 4000) { r.ok = false; return false; }  // lib0 readAny recurses without a limit (V8 overflows its stack near here)
+bool skip_any(JRd& r, int depth) {
+  if (depth > (int)ANY_HOST_DEPTH) { r.ok = false; return false; }
   const uint32_t tag = r.u8();
   switch (tag) {
     case 127: case 126: case 121: case 120: return r.ok;
@@ -200,124 +39,102 @@ bool skip_any(Rd& r, int depth) {
   }
 }
 
-uint32_t utf8_len(unsigned char c) { return c < 0x80u ? 1u : c < 0xE0u ? 2u : c < 0xF0u ? 3u : 4u; }
-
 struct JsonCtx {
+  explicit JsonCtx(const HostView& view) : v(view) {}
   const HostView& v;
-  int depth = 0;
+  int depth = 0;               // nested types open
+  uint32_t rem[ANY_HOST_DEPTH];
+  JStack<ANY_HOST_DEPTH> st{rem};  // (one `any` value at a time uses it)
 };
 
 void type_json(JsonCtx& c, uint32_t parent_unit, uint32_t type_ref, const ViewKey* array_list, std::string& o);
 
-// every element of a visible view segment, as JSON values (undefined kept as a flag)
-void seg_elements(JsonCtx& c, const ViewSeg& s, std::vector<std::pair<bool, std::string>>& out, bool last_only) {
-  const HostView& v = c.v;
-  Rd r{v.bytes.data(), s.b0, s.b1};
-  const uint32_t n = last_only ? 1u : s.len;
-  switch (s.ref) {
-    case R_ANY:
-      for (uint32_t i = 0; i < n && r.ok; ++i) {
-        std::string e;
-        const bool def = any_json(r, e, 0);
-        out.push_back({def, e});
-      }
-      return;
-    case R_JSON:
-      for (uint32_t i = 0; i < n && r.ok; ++i) {
-        const uint32_t k = r.vu();
-        const uint8_t* q = r.take(k);
-        if (!r.ok) return;
-        const std::string t((const char*)q, k);
-        out.push_back({t != "undefined", t});
-      }
-      return;
-    case R_STRING: {  // one element per UTF-16 code unit; astral characters stay whole
-      size_t p = s.b0;
-      while (p < s.b1) {
-        const uint32_t l = std::min<uint32_t>(utf8_len(v.bytes[p]), (uint32_t)(s.b1 - p));
-        std::string e;
-        put_json_str(e, v.bytes.data() + p, l);
-        out.push_back({true, e});
-        p += l;
-      }
-      return;
-    }
-    case R_BINARY: {
-      const uint32_t k = r.vu();
-      const uint8_t* q = r.take(k);
-      std::string e;
-      if (r.ok) put_uint8array(e, q, k);
-      out.push_back({true, e});
-      return;
-    }
-    case R_TYPE: {
-      const uint32_t tr = r.vu();
-      std::string e;
+SegCursor cursor(const HostView& v, const ViewSeg& s, bool entry) { return SegCursor(v.bytes.data(), s.b0, s.b1, s.ref, s.len, entry); }
+
+// The next element of segment `s` appended to `o`: 0 none left, 1 written, 2 `undefined` (nothing
+// written) — the states of view_map_get / view_array_get. Content that is truncated inside its
+// segment, or an `any` nested past ANY_HOST_DEPTH, is written null.
+int put_element(JsonCtx& c, SegCursor& cur, const ViewSeg& s, std::string& o) {
+  const size_t mark = o.size();
+  JString w{o};
+  switch (cur.next(w, c.st)) {
+    case EL_OK: return 1;
+    case EL_UNDEF: return 2;
+    case EL_END: return 0;
+    case EL_TYPE:
       if (c.depth < 512) {
         ++c.depth;
-        type_json(c, s.unit + s.len - 1, tr, nullptr, e);
+        type_json(c, s.unit + s.len - 1, cur.type_ref, nullptr, o);
         --c.depth;
       }
-      out.push_back({true, e});
-      return;
-    }
-    case R_EMBED: {
-      const uint32_t k = r.vu();
-      const uint8_t* q = r.take(k);
-      out.push_back({true, r.ok ? std::string((const char*)q, k) : std::string("null")});
-      return;
-    }
-    case R_FORMAT:  // ContentFormat.getContent() is [] (Y@72137 area): a map entry's value is undefined
-      out.push_back({false, std::string()});
-      return;
+      return 1;
     default:
-      out.push_back({true, "null"});  // ContentDoc is outside crdt.c
+      o.resize(mark);
+      o += "null";
+      return 1;
   }
 }
 
-void map_json(JsonCtx& c, uint32_t parent_unit, std::string& o) {
+bool entry_live(const ViewKey& K) {
+  return (K.flags & VK_PSUB) && (K.win.flags & VS_SET) && !(K.win.flags & VS_DELETED) && (K.win.flags & VS_ITEM);
+}
+
+// The live entries among `ks` as a JSON object: "name":value, the value being the last element of
+// the entry's winning item (typeMapGetAll Y@49897), an undefined one omitted. `ids`: every value as
+// ["client:clock" of the winning item, value].
+void put_entries(JsonCtx& c, const std::vector<uint32_t>* ks, bool ids, std::string& o) {
   const HostView& v = c.v;
   o.push_back('{');
-  bool first = true;
-  auto it = v.by_parent.find(parent_unit);
-  if (it != v.by_parent.end()) {
-    for (uint32_t ki : it->second) {
+  const size_t open = o.size();
+  if (ks)
+    for (uint32_t ki : *ks) {
       const ViewKey& K = v.keys[ki];
-      if (!(K.flags & VK_PSUB) || !(K.win.flags & VS_SET) || (K.win.flags & VS_DELETED) || !(K.win.flags & VS_ITEM)) continue;
-      std::vector<std::pair<bool, std::string>> el;
-      seg_elements(c, K.win, el, true);
-      if (el.empty() || !el.back().first) continue;
-      if (!first) o.push_back(',');
-      first = false;
-      put_json_str(o, v.bytes.data() + K.psub_pos, K.psub_len);
+      if (!entry_live(K)) continue;
+      const size_t mark = o.size();
+      if (mark != open) o.push_back(',');
+      JString w{o};
+      json_put_str(w, v.bytes.data() + K.psub_pos, K.psub_len);
       o.push_back(':');
-      o += el.back().second;
+      if (ids) o += "[\"" + std::to_string(K.win.client) + ":" + std::to_string(K.win.clock + K.win.len - 1) + "\",";
+      SegCursor cur = cursor(v, K.win, true);
+      if (put_element(c, cur, K.win, o) != 1) { o.resize(mark); continue; }
+      if (ids) o.push_back(']');
     }
-  }
   o.push_back('}');
 }
 
+const std::vector<uint32_t>* members_of(const HostView& v, uint32_t parent_unit) {
+  const auto it = v.by_parent.find(parent_unit);
+  return it == v.by_parent.end() ? nullptr : &it->second;
+}
+const std::vector<uint32_t>* root_entries_of(const HostView& v, const std::string& name) {
+  const auto it = v.root_entries.find(name);
+  return it == v.root_entries.end() ? nullptr : &it->second;
+}
+
 const ViewKey* list_of(const HostView& v, uint32_t parent_unit) {
-  auto it = v.by_parent.find(parent_unit);
-  if (it == v.by_parent.end()) return nullptr;
-  for (uint32_t ki : it->second)
-    if (!(v.keys[ki].flags & VK_PSUB)) return &v.keys[ki];
+  if (const auto* ks = members_of(v, parent_unit))
+    for (uint32_t ki : *ks)
+      if (!(v.keys[ki].flags & VK_PSUB)) return &v.keys[ki];
   return nullptr;
 }
 
-void array_json(JsonCtx& c, const ViewKey* L, std::string& o) {
+bool visible(const ViewSeg& s) { return (s.flags & VS_ITEM) && !(s.flags & VS_DELETED) && (s.flags & VS_COUNTABLE); }
+
+void array_json(JsonCtx& c, const ViewKey* L, std::string& o) {  // typeListToArray (Y@46408)
   o.push_back('[');
-  bool first = true;
+  const size_t open = o.size();
   if (L) {
     for (uint32_t i = 0; i < L->nseg; ++i) {
       const ViewSeg& s = c.v.segs[L->seg0 + i];
-      if ((s.flags & VS_DELETED) || !(s.flags & VS_COUNTABLE) || !(s.flags & VS_ITEM)) continue;
-      std::vector<std::pair<bool, std::string>> el;
-      seg_elements(c, s, el, false);
-      for (auto& e : el) {
-        if (!first) o.push_back(',');
-        first = false;
-        o += e.first ? e.second : std::string("null");
+      if (!visible(s)) continue;
+      SegCursor cur = cursor(c.v, s, false);
+      for (;;) {
+        const size_t mark = o.size();
+        if (mark != open) o.push_back(',');
+        const int st = put_element(c, cur, s, o);
+        if (st == 0) { o.resize(mark); break; }
+        if (st == 2) o += "null";
       }
     }
   }
@@ -329,16 +146,17 @@ void text_json(JsonCtx& c, const ViewKey* L, std::string& o) {  // YText.toJSON:
   if (L)
     for (uint32_t i = 0; i < L->nseg; ++i) {
       const ViewSeg& g = c.v.segs[L->seg0 + i];
-      if ((g.flags & VS_DELETED) || !(g.flags & VS_ITEM) || g.ref != R_STRING) continue;
+      if ((g.flags & VS_DELETED) || !(g.flags & VS_ITEM) || g.ref != REF_STRING) continue;
       s.append((const char*)c.v.bytes.data() + g.b0, g.b1 - g.b0);
     }
-  put_json_str(o, (const uint8_t*)s.data(), s.size());
+  JString w{o};
+  json_put_str(w, (const uint8_t*)s.data(), s.size());
 }
 
 // YMap (1) -> object, YText (2) -> string, XML types -> "" (XmlElement.toJSON is its XML text,
 // outside crdt.c), everything else (YArray) -> array
 void type_json(JsonCtx& c, uint32_t parent_unit, uint32_t type_ref, const ViewKey* array_list, std::string& o) {
-  if (type_ref == 1) { map_json(c, parent_unit, o); return; }
+  if (type_ref == 1) { put_entries(c, members_of(c.v, parent_unit), false, o); return; }
   const ViewKey* L = array_list ? array_list : list_of(c.v, parent_unit);
   if (type_ref == 2) { text_json(c, L, o); return; }
   if (type_ref >= 3 && type_ref <= 6) { o += "\"\""; return; }
@@ -374,11 +192,11 @@ struct ParentRef {
 int resolve_parent(const HostView& v, const OpTarget& t, uint32_t want_type, ParentRef& pr, std::string& err) {
   if (!t.nested) { pr.root = true; pr.unit = VNONE; return YCRDT_OK; }
   const ViewKey* e = v.root_list(t.root, &t.key);
-  if (!e || !(e->win.flags & VS_SET) || (e->win.flags & VS_DELETED) || e->win.ref != R_TYPE) {
+  if (!e || !(e->win.flags & VS_SET) || (e->win.flags & VS_DELETED) || e->win.ref != REF_TYPE) {
     err = "no shared type at " + t.root + "." + t.key;
     return YCRDT_E_ARG;
   }
-  Rd r{v.bytes.data(), e->win.b0, e->win.b1};
+  JRd r{v.bytes.data(), e->win.b0, e->win.b1, true};
   const uint32_t tr = r.vu();
   if (!r.ok || tr != want_type) { err = "type mismatch at " + t.root + "." + t.key; return YCRDT_E_ARG; }
   pr.root = false;
@@ -435,8 +253,6 @@ void write_ds_update(std::vector<uint8_t>& o, std::vector<std::array<uint32_t, 3
   }
 }
 
-bool visible(const ViewSeg& s) { return (s.flags & VS_ITEM) && !(s.flags & VS_DELETED) && (s.flags & VS_COUNTABLE); }
-
 }  // namespace
 
 namespace {
@@ -489,37 +305,17 @@ const ViewKey* HostView::child_list(uint32_t unit, const std::string* psub) cons
 
 int view_type_at(const HostView& v, const std::string& root, const std::string& key) {
   const ViewKey* e = v.root_list(root, &key);
-  if (!e || !(e->win.flags & VS_SET) || (e->win.flags & VS_DELETED) || e->win.ref != R_TYPE) return -1;
-  Rd r{v.bytes.data(), e->win.b0, e->win.b1};
+  if (!e || !(e->win.flags & VS_SET) || (e->win.flags & VS_DELETED) || e->win.ref != REF_TYPE) return -1;
+  JRd r{v.bytes.data(), e->win.b0, e->win.b1, true};
   const uint32_t tr = r.vu();
   return r.ok ? (int)tr : -1;
 }
 
 bool view_root_json(const HostView& v, const std::string& name, int kind, std::string& out, std::string& err) {
-  JsonCtx c{v};
+  JsonCtx c(v);
   out.clear();
-  if (kind == 0) {
-    // root map entries: every root list named `name` with a parentSub
-    out.push_back('{');
-    bool first = true;
-    auto it = v.root_entries.find(name);
-    if (it != v.root_entries.end())
-      for (uint32_t ki : it->second) {
-        const ViewKey& K = v.keys[ki];
-        if (!(K.win.flags & VS_SET) || (K.win.flags & VS_DELETED) || !(K.win.flags & VS_ITEM)) continue;
-        std::vector<std::pair<bool, std::string>> el;
-        seg_elements(c, K.win, el, true);
-        if (el.empty() || !el.back().first) continue;
-        if (!first) out.push_back(',');
-        first = false;
-        put_json_str(out, v.bytes.data() + K.psub_pos, K.psub_len);
-        out.push_back(':');
-        out += el.back().second;
-      }
-    out.push_back('}');
-    return true;
-  }
-  array_json(c, v.root_list(name, nullptr), out);
+  if (kind == 0) put_entries(c, root_entries_of(v, name), false, out);  // every root list named `name` with a parentSub
+  else array_json(c, v.root_list(name, nullptr), out);
   return true;
 }
 
@@ -535,7 +331,7 @@ bool view_type_json(const HostView& v, const OpTarget& t, int kind, std::string&
     out = kind == 0 ? "{}" : "[]";
     return true;
   }
-  JsonCtx c{v};
+  JsonCtx c(v);
   type_json(c, pr.unit, kind == 0 ? 1u : 0u, nullptr, out);
   return true;
 }
@@ -545,35 +341,14 @@ bool view_type_json(const HostView& v, const OpTarget& t, int kind, std::string&
 // winning item changed — the same value set again is a new item — so the facade's map observers
 // compare these ids, not the values (and nested-type contents never count, as in YMap.observe).
 bool view_map_entries(const HostView& v, const OpTarget& t, std::string& out) {
-  out = "{";
-  std::vector<uint32_t> ks;
-  if (!t.nested) {
-    auto it = v.root_entries.find(t.root);
-    if (it != v.root_entries.end()) ks = it->second;
-  } else {
-    ParentRef pr;
-    std::string err;
-    if (resolve_parent(v, t, 1, pr, err) == YCRDT_OK) {
-      auto it = v.by_parent.find(pr.unit);
-      if (it != v.by_parent.end()) ks = it->second;
-    }
-  }
-  JsonCtx c{v};
-  bool first = true;
-  for (uint32_t ki : ks) {
-    const ViewKey& K = v.keys[ki];
-    if (!(K.flags & VK_PSUB) || !(K.win.flags & VS_SET) || (K.win.flags & VS_DELETED) || !(K.win.flags & VS_ITEM)) continue;
-    std::vector<std::pair<bool, std::string>> el;
-    seg_elements(c, K.win, el, true);
-    if (el.empty() || !el.back().first) continue;
-    if (!first) out.push_back(',');
-    first = false;
-    put_json_str(out, v.bytes.data() + K.psub_pos, K.psub_len);
-    out += ":[\"" + std::to_string(K.win.client) + ":" + std::to_string(K.win.clock + K.win.len - 1) + "\",";
-    out += el.back().second;
-    out.push_back(']');
-  }
-  out.push_back('}');
+  out.clear();
+  const std::vector<uint32_t>* ks = nullptr;
+  ParentRef pr;
+  std::string err;
+  if (!t.nested) ks = root_entries_of(v, t.root);
+  else if (resolve_parent(v, t, 1, pr, err) == YCRDT_OK) ks = members_of(v, pr.unit);
+  JsonCtx c(v);
+  put_entries(c, ks, true, out);
   return true;
 }
 
@@ -593,12 +368,9 @@ void view_map_get(const HostView& v, const OpTarget& t, const std::string& key, 
   const ViewKey* K = read_list(v, t, 1, &key);
   if (!K || !(K->win.flags & VS_SET) || (K->win.flags & VS_DELETED) || !(K->win.flags & VS_ITEM)) return;
   // typeMapGet (Y@49897): the last element of the entry's winning item
-  JsonCtx c{v};
-  std::vector<std::pair<bool, std::string>> el;
-  seg_elements(c, K->win, el, true);
-  if (el.empty()) return;
-  state = el.back().first ? 1 : 2;
-  if (state == 1) json = el.back().second;
+  JsonCtx c(v);
+  SegCursor cur = cursor(v, K->win, true);
+  state = put_element(c, cur, K->win, json);
 }
 
 uint32_t view_map_size(const HostView& v, const OpTarget& t) {
@@ -639,19 +411,18 @@ void view_array_get(const HostView& v, const OpTarget& t, uint64_t index, int& s
     const ViewSeg& s = v.segs[L->seg0 + i];
     if (!visible(s)) continue;
     if (index >= s.len) { index -= s.len; continue; }
-    JsonCtx c{v};
-    std::vector<std::pair<bool, std::string>> el;
-    seg_elements(c, s, el, false);
-    if (index >= el.size()) return;
+    JsonCtx c(v);
+    SegCursor cur = cursor(v, s, false);
+    JText skipped{nullptr, 0};  // (counts only; a nested type is not written at all)
+    for (; index; --index) cur.next(skipped, c.st);
     // YArray.get of an `undefined` element: toJSON writes null there, get returns undefined
-    state = el[index].first ? 1 : 2;
-    if (state == 1) json = el[index].second;
+    state = put_element(c, cur, s, json);
     return;
   }
 }
 
 bool any_values_ok(const uint8_t* p, size_t n, uint32_t count) {
-  Rd r{p, 0, n};
+  JRd r{p, 0, n, true};
   for (uint32_t i = 0; i < count && r.ok; ++i) skip_any(r, 0);
   return r.ok && r.p == n;
 }
@@ -722,7 +493,7 @@ int encode_array_insert(const HostView& v, const OpTarget& t, uint32_t index, co
   std::vector<uint8_t> content;
   w_vu(content, count);
   content.insert(content.end(), anys, anys + len);
-  write_item_update(out, client, clock, R_ANY, origin, rorigin, t, pr, nullptr, content.data(), content.size());
+  write_item_update(out, client, clock, REF_ANY, origin, rorigin, t, pr, nullptr, content.data(), content.size());
   return YCRDT_OK;
 }
 

@@ -1,7 +1,8 @@
 // yc_host.h — host side of the materialised view: crdt.c JSON (YMap.toJSON / YArray.toJSON) and
 // the encoders of local ops (YMap.set / delete, YArray.insert / delete) as Yjs v1 updates.
 // Pure host C++ (no HIP): the device computes winners and list order (yc_view.hip); this file only
-// decodes the values at the byte ranges the view hands over and writes new structs.
+// decodes the values at the byte ranges the view hands over and writes new structs. The JSON text
+// of the values is defined in yc_json.h, for this writer and the fleet toJSON kernels alike.
 #pragma once
 #include <cstdint>
 #include <string>

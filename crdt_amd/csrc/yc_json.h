@@ -1,25 +1,30 @@
-// yc_json.h — JSON.stringify text of lib0 `any` values, for the host and the device alike.
+// yc_json.h — the JSON.stringify text of view content, defined once for the host and the device.
 //
-// any_json_text restates any_json of yc_host.cpp (lib0 readAny L0@1937 -> JSON.stringify) without
-// recursion and without allocation, so that the fleet toJSON kernels (yc_json.hip) write the same
-// bytes the host writer does: undefined members are dropped from objects and written null in
+// any_json_text writes one lib0 `any` value (lib0 readAny L0@1937 -> JSON.stringify) without
+// recursion and without allocation: undefined members are dropped from objects and written null in
 // arrays, numbers take Number::toString's text (yc_num.h), float32 is widened, BigInt64 is its
-// signed decimal, a Uint8Array is {"0":b0,...}, strings are escaped as put_json_str does, object
-// members keep their encoded order. One function sizes (out == nullptr) and writes.
+// signed decimal, a Uint8Array is {"0":b0,...}, object members keep their encoded order. SegCursor
+// walks the elements of one view segment, whatever its content kind. Both write into a sink and
+// keep their open containers on a stack the caller hands in: the fleet toJSON kernels (yc_json.hip)
+// pass JText (one function sizes, o == nullptr, and writes) and 64 levels, the host writer
+// (yc_host.cpp) appends to a std::string through JString and follows ANY_HOST_DEPTH levels. So the
+// per-document answers and the fleet answers are the same bytes by construction.
 #pragma once
 #include <cstdint>
 #include <cstring>
+#include <string>
 
 #include "yc_parse.h"  // YC_HD, yc_num.h
 
 namespace yc {
 
-constexpr uint32_t ANY_JSON_DEPTH = 64;  // container levels of one `any` value the writer follows
+constexpr uint32_t ANY_JSON_DEPTH = 64;    // container levels of one `any` value the device follows
+constexpr uint32_t ANY_HOST_DEPTH = 4000;  // ... the host follows (lib0 readAny recurses without a limit; V8 overflows its stack near here)
 enum : uint32_t {
   AJ_OK = 0,
   AJ_UNDEF = 1,  // the value is `undefined`: nothing written (a map entry is omitted, an array member is null)
   AJ_BAD = 2,    // truncated or not an `any` encoding
-  AJ_DEEP = 3,   // nested past ANY_JSON_DEPTH: the caller takes the host writer
+  AJ_DEEP = 3,   // nested past the caller's stack (the device: the host writer answers)
 };
 
 struct JText {        // byte sink at position n; o == nullptr only counts; nothing is stored at or past cap
@@ -38,7 +43,18 @@ struct JText {        // byte sink at position n; o == nullptr only counts; noth
   }
 };
 
-YC_HD inline void json_put_esc(JText& o, const uint8_t* s, uint64_t n) {  // put_json_str (yc_host.cpp) without the quotes
+struct JString {         // the host sink: appends to a string
+  std::string& s;
+  void ch(uint32_t c) { s.push_back((char)c); }
+  void lit(const char* t) { s += t; }
+  void raw(const uint8_t* t, uint64_t k) { s.append((const char*)t, k); }
+  uint64_t n() const { return s.size(); }
+};
+
+YC_HDI uint32_t utf8_len(uint32_t c) { return c < 0x80u ? 1u : c < 0xE0u ? 2u : c < 0xF0u ? 3u : 4u; }
+
+template <class Sink>
+YC_HD inline void json_put_esc(Sink& o, const uint8_t* s, uint64_t n) {  // a JSON string's text without the quotes
   for (uint64_t i = 0; i < n; ++i) {
     const uint32_t c = s[i];
     switch (c) {
@@ -60,20 +76,23 @@ YC_HD inline void json_put_esc(JText& o, const uint8_t* s, uint64_t n) {  // put
     }
   }
 }
-YC_HD inline void json_put_str(JText& o, const uint8_t* s, uint64_t n) {
+template <class Sink>
+YC_HD inline void json_put_str(Sink& o, const uint8_t* s, uint64_t n) {
   o.ch('"');
   json_put_esc(o, s, n);
   o.ch('"');
 }
 
-YC_HD inline void json_put_u64(JText& o, uint64_t v) {
+template <class Sink>
+YC_HD inline void json_put_u64(Sink& o, uint64_t v) {
   char t[20];
   uint32_t k = 0;
   do { t[k++] = (char)('0' + v % 10); v /= 10; } while (v);
   while (k) o.ch((uint8_t)t[--k]);
 }
 
-YC_HD inline void json_put_number(JText& o, double x) {  // JSON.stringify(Number)
+template <class Sink>
+YC_HD inline void json_put_number(Sink& o, double x) {  // JSON.stringify(Number)
   uint64_t u;
   memcpy(&u, &x, 8);
   if (((u >> 52) & 0x7ffu) == 0x7ffu) { o.lit("null"); return; }  // NaN, +-Infinity
@@ -85,7 +104,8 @@ YC_HD inline void json_put_number(JText& o, double x) {  // JSON.stringify(Numbe
   o.raw((const uint8_t*)t, len);
 }
 
-YC_HD inline void json_put_bytes(JText& o, const uint8_t* p, uint64_t n) {  // JSON.stringify(Uint8Array)
+template <class Sink>
+YC_HD inline void json_put_bytes(Sink& o, const uint8_t* p, uint64_t n) {  // JSON.stringify(Uint8Array)
   o.ch('{');
   for (uint64_t i = 0; i < n; ++i) {
     if (i) o.ch(',');
@@ -98,7 +118,7 @@ YC_HD inline void json_put_bytes(JText& o, const uint8_t* p, uint64_t n) {  // J
   o.ch('}');
 }
 
-struct JRd {  // bounded reader over b[p, end): the lib0 0.2.42 forms of yc_host.cpp's Rd
+struct JRd {  // bounded reader over b[p, end): the lib0 0.2.42 forms
   const uint8_t* b;
   uint64_t p, end;
   bool ok;
@@ -140,35 +160,63 @@ struct JRd {  // bounded reader over b[p, end): the lib0 0.2.42 forms of yc_host
   }
 };
 
+// The open containers of one `any` value: members left (in the caller's N words, an array of its
+// own so that the rest stays in registers on the device), object or array, nothing written yet.
+template <uint32_t N>
+struct JStack {
+  static constexpr uint32_t W = (N + 63) / 64;
+  uint32_t* rem;
+  uint64_t obj[W], fresh[W];  // one bit per level; a word is cleared when its first level opens
+  uint32_t depth;
+  YC_HDI explicit JStack(uint32_t* words) : rem(words), depth(0) {}
+  YC_HDI static uint32_t word(uint32_t t) { return W == 1 ? 0u : t >> 6; }
+  YC_HDI bool push(bool is_obj, uint32_t members) {  // false: full
+    if (depth == N) return false;
+    const uint64_t bit = 1ull << (depth & 63u);
+    const uint32_t w = word(depth);
+    if (bit == 1) obj[w] = fresh[w] = 0;
+    rem[depth++] = members;
+    fresh[w] |= bit;
+    if (is_obj) obj[w] |= bit; else obj[w] &= ~bit;
+    return true;
+  }
+  YC_HDI uint32_t& top() { return rem[depth - 1]; }  // members left
+  YC_HDI bool top_obj() const { return (obj[word(depth - 1)] >> ((depth - 1) & 63u)) & 1u; }
+  YC_HDI bool take_fresh() {  // true once per level: its first written member takes no comma
+    const uint64_t bit = 1ull << ((depth - 1) & 63u);
+    uint64_t& f = fresh[word(depth - 1)];
+    const bool was = (f & bit) != 0;
+    f &= ~bit;
+    return was;
+  }
+  YC_HDI void pop() { --depth; }
+};
+
 // One lib0 `any` value at b[p, end) as JSON text appended to `o`; p moves past the value. Iterative:
-// an explicit stack of (kind, remaining members, nothing written yet) per open container.
-YC_HD inline uint32_t any_json_text(const uint8_t* b, uint64_t& p, uint64_t end, JText& o) {
+// `st` holds one level per open container.
+template <class Sink, class Stack>
+YC_HD inline uint32_t any_json_text(const uint8_t* b, uint64_t& p, uint64_t end, Sink& o, Stack& st) {
   JRd r{b, p, end, true};
-  uint32_t rem[ANY_JSON_DEPTH];
-  uint64_t is_obj = 0, first = 0;  // one bit per level
-  uint32_t depth = 0;
+  st.depth = 0;
   for (;;) {
-    if (depth) {
-      const uint32_t t = depth - 1;
-      const uint64_t bit = 1ull << t;
-      if (rem[t] == 0) {
-        o.ch((is_obj & bit) ? '}' : ']');
-        if (--depth == 0) break;
+    if (st.depth) {
+      if (st.top() == 0) {
+        o.ch(st.top_obj() ? '}' : ']');
+        st.pop();
+        if (st.depth == 0) break;
         continue;
       }
-      --rem[t];
-      if (is_obj & bit) {
+      --st.top();
+      if (st.top_obj()) {
         const uint32_t kl = r.vu();
         const uint8_t* k = r.take(kl);
         if (!r.ok) return AJ_BAD;
         if (r.p < r.end && b[r.p] == 127) { ++r.p; continue; }  // an undefined member is dropped
-        if (!(first & bit)) o.ch(',');
-        first &= ~bit;
+        if (!st.take_fresh()) o.ch(',');
         json_put_str(o, k, kl);
         o.ch(':');
       } else {
-        if (!(first & bit)) o.ch(',');
-        first &= ~bit;
+        if (!st.take_fresh()) o.ch(',');
         if (r.p < r.end && b[r.p] == 127) { ++r.p; o.lit("null"); continue; }
       }
     }
@@ -196,7 +244,7 @@ YC_HD inline uint32_t any_json_text(const uint8_t* b, uint64_t& p, uint64_t end,
           double d;
           memcpy(&d, &u, 8);
           json_put_number(o, d);
-        } else {  // BigInt64: its signed decimal
+        } else {  // BigInt64 (JSON.stringify would throw): its signed decimal
           if (u >> 63) { o.ch('-'); u = ~u + 1; }
           json_put_u64(o, u);
         }
@@ -209,23 +257,88 @@ YC_HD inline uint32_t any_json_text(const uint8_t* b, uint64_t& p, uint64_t end,
       case 118: case 117: {
         const uint32_t n = r.vu();
         if (!r.ok) break;
-        if (depth == ANY_JSON_DEPTH) return AJ_DEEP;
-        rem[depth] = n;
-        const uint64_t bit = 1ull << depth;
-        first |= bit;
-        if (tag == 118) is_obj |= bit; else is_obj &= ~bit;
-        ++depth;
+        if (!st.push(tag == 118, n)) return AJ_DEEP;
         o.ch(tag == 118 ? '{' : '[');
         continue;
       }
       default: return AJ_BAD;
     }
     if (!r.ok) return AJ_BAD;
-    if (depth == 0) break;
+    if (st.depth == 0) break;
   }
   p = r.p;
   return AJ_OK;
 }
+
+// The elements of one visible view segment (its content bytes b[b0, b1), b0 <= b1 inside the
+// buffer), one per next(): ContentAny and ContentJSON hold `len` values, a ContentString one
+// element per UTF-8 character (a truncated tail clipped to the segment), ContentBinary,
+// ContentEmbed and ContentType one, a ContentFormat one `undefined` (getContent() is []), anything
+// else (ContentDoc is outside crdt.c) one null. `entry`: the value of a YMap entry, that is one
+// element — of a ContentString the last character, of an empty string nothing.
+enum : uint32_t {
+  EL_OK = 0,     // one element written
+  EL_UNDEF = 1,  // the element is `undefined`: nothing written (an entry is omitted, a list member is null)
+  EL_END = 2,    // no element left
+  EL_BAD = 3,    // truncated or malformed content (what was written of it stays in the sink); END follows
+  EL_DEEP = 4,   // an `any` nested past the stack; END follows
+  EL_TYPE = 5,   // a ContentType of type ref `type_ref`: nothing written, the caller writes the nested type
+};
+struct SegCursor {
+  JRd r;
+  uint32_t ref, left, type_ref = 0;
+  YC_HDI SegCursor(const uint8_t* b, uint64_t b0, uint64_t b1, uint32_t ref_, uint32_t len, bool entry)
+      : r{b, b0, b1, true}, ref(ref_), left(ref_ == REF_ANY || ref_ == REF_JSON ? (entry ? 1u : len) : 1u) {
+    if (entry && ref == REF_STRING)  // (a string ends where its bytes end: `left` is not read)
+      for (uint64_t p = b0; p < b1; p += utf8_len(b[p])) r.p = p;
+  }
+  YC_HDI uint32_t stop(uint32_t e) { left = 0; r.p = r.end; return e; }
+  template <class Sink, class Stack>
+  YC_HD inline uint32_t next(Sink& o, Stack& st) {
+    if (ref == REF_STRING) {
+      if (r.p >= r.end) return EL_END;
+      uint64_t l = utf8_len(r.b[r.p]);
+      if (l > r.end - r.p) l = r.end - r.p;
+      json_put_str(o, r.b + r.p, l);
+      r.p += l;
+      return EL_OK;
+    }
+    if (!left) return EL_END;
+    --left;
+    switch (ref) {
+      case REF_ANY: {
+        uint64_t p = r.p;
+        const uint32_t a = any_json_text(r.b, p, r.end, o, st);
+        if (a == AJ_BAD || a == AJ_DEEP) return stop(a == AJ_BAD ? EL_BAD : EL_DEEP);
+        r.p = p;
+        return a == AJ_UNDEF ? EL_UNDEF : EL_OK;
+      }
+      case REF_JSON: {
+        const uint32_t k = r.vu();
+        const uint8_t* q = r.take(k);
+        if (!r.ok) return stop(EL_BAD);
+        const char* u = "undefined";
+        bool undef = k == 9;
+        for (uint32_t j = 0; undef && j < 9; ++j) undef = q[j] == (uint8_t)u[j];
+        if (undef) return EL_UNDEF;
+        o.raw(q, k);
+        return EL_OK;
+      }
+      case REF_BINARY: case REF_EMBED: {
+        const uint32_t k = r.vu();
+        const uint8_t* q = r.take(k);
+        if (!r.ok) return stop(EL_BAD);
+        if (ref == REF_BINARY) json_put_bytes(o, q, k); else o.raw(q, k);
+        return EL_OK;
+      }
+      case REF_TYPE:
+        type_ref = r.vu();
+        return r.ok ? EL_TYPE : stop(EL_BAD);
+      case REF_FORMAT: return EL_UNDEF;
+      default: o.lit("null"); return EL_OK;
+    }
+  }
+};
 
 }  // namespace yc
 

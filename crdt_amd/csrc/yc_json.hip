@@ -18,7 +18,8 @@
 //   k_jwrite      sweep 3: every placed item writes its own bytes, all in parallel
 // Whatever the bounds refuse (entry names past JSON_NAME_MAX, types nested past JSON_DEPTH_MAX, an
 // `any` past ANY_JSON_DEPTH, malformed content) leaves its item unsized, which leaves every
-// container above it unsized: the request is flagged and the host answers it through ycrdt_doc_json.
+// container above it unsized: the request is flagged and the host answers it through ycrdt_doc_json,
+// whose writer (yc_host.cpp) is built from the same value writer and segment cursor (yc_json.h).
 #include "yc_common.h"
 #include "yc_json.h"
 
@@ -30,7 +31,6 @@ constexpr uint64_t NONE64 = ~0ull;
 constexpr uint64_t TEXT_BIT = 1ull << 63;
 enum : uint32_t { JS_OPEN = 0, JS_SIZED = 1, JS_REFUSED = 2 };
 enum : uint32_t { EM_OK = 0, EM_OMIT = 1, EM_PENDING = 2, EM_REFUSED = 3 };
-enum : uint32_t { R_JSON = 2, R_BINARY = 3, R_STRING = 4, R_EMBED = 5, R_FORMAT = 6, R_TYPE = 7, R_ANY = 8 };
 enum : uint32_t { BOX_MAP = 0, BOX_ARRAY = 1, BOX_TEXT = 2, BOX_XML = 3 };
 
 __device__ __forceinline__ uint64_t ld64(const uint64_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -55,19 +55,13 @@ __device__ __forceinline__ uint32_t upper_bound_u64(const uint64_t* __restrict__
 
 __device__ __forceinline__ bool in_bytes(const JsonArgs& a, uint32_t pos, uint32_t len) { return (uint64_t)pos + len <= a.nbytes; }
 
-__device__ __forceinline__ uint32_t name_hash(const uint8_t* p, uint32_t n) {  // FNV-1a (the host hashes the requests alike)
-  uint32_t h = 2166136261u;
-  for (uint32_t i = 0; i < n; ++i) h = (h ^ p[i]) * 16777619u;
-  return h;
-}
-
 // the container a view key belongs to: its parent type item's unit, or (document, root name)
 __device__ __forceinline__ uint64_t group_key(const JsonArgs& a, const ViewKey& K) {
   if (K.parent_unit != VNONE) return K.parent_unit;
   const uint32_t r = K.slot < a.ck ? a.krep[K.slot] : VNONE;
   if (r == VNONE || !in_bytes(a, K.name_pos, K.name_len)) return NONE64;
   const uint32_t doc = a.cl_doc ? a.cl_doc[a.g_cidx[r]] : 0u;
-  return (1ull << 63) | ((uint64_t)(doc & 0x7FFFFFFFu) << 32) | (name_hash(a.bytes + K.name_pos, K.name_len) >> 1);
+  return (1ull << 63) | ((uint64_t)(doc & 0x7FFFFFFFu) << 32) | (fnv_key(a.bytes, K.name_pos, K.name_len) >> 1);  // (the host hashes the requests alike)
 }
 
 __global__ void k_jsort_key(JsonArgs a, uint32_t pass, const uint32_t* __restrict__ ord_in, uint64_t* __restrict__ key) {
@@ -178,107 +172,41 @@ __device__ __forceinline__ Box type_box(const JsonArgs& a, uint32_t unit, uint32
   return b;
 }
 
-__device__ __forceinline__ uint32_t utf8_len(uint32_t c) { return c < 0x80u ? 1u : c < 0xE0u ? 2u : c < 0xF0u ? 3u : 4u; }
-
-// The elements of a visible view segment as JSON (seg_elements of yc_host.cpp). `entry`: a YMap
-// entry's value — its one element, nothing behind it, EM_OMIT when it is undefined; otherwise every
+// The elements of a visible view segment as JSON (SegCursor, yc_json.h). `entry`: a YMap entry's
+// value — its one element, nothing behind it, EM_OMIT when it is undefined; otherwise every
 // element followed by a separator, except the one that would stand where the container closes.
 __device__ __forceinline__ uint32_t emit_seg(const JsonArgs& a, const ViewSeg& s, bool entry, bool scans, JText& o, uint64_t cend) {
   if (s.b0 > s.b1 || s.b1 > a.nbytes) return EM_REFUSED;
-  auto sep = [&]() {
-    if (!entry && (!o.o || o.n != cend)) o.ch(',');
-  };
-  JRd r{a.bytes, s.b0, s.b1, true};
-  const uint32_t n = entry ? 1u : s.len;
-  switch (s.ref) {
-    case R_ANY:
-      for (uint32_t i = 0; i < n; ++i) {
-        uint64_t p = r.p;
-        const uint32_t st = any_json_text(a.bytes, p, s.b1, o);
-        if (st == AJ_BAD || st == AJ_DEEP) return EM_REFUSED;
-        r.p = p;
-        if (st == AJ_UNDEF) {
-          if (entry) return EM_OMIT;
-          o.lit("null");
+  SegCursor c(a.bytes, s.b0, s.b1, s.ref, s.len, entry);
+  uint32_t rem[ANY_JSON_DEPTH];
+  JStack<ANY_JSON_DEPTH> st(rem);
+  for (;;) {
+    switch (c.next(o, st)) {
+      case EL_OK: break;
+      case EL_UNDEF:
+        if (entry) return EM_OMIT;
+        o.lit("null");
+        break;
+      case EL_END: return entry ? EM_OMIT : EM_OK;  // (an entry returns at its element: this one has none)
+      case EL_TYPE: {
+        if (!scans) return EM_PENDING;
+        const Box b = type_box(a, s.unit + s.len - 1, c.type_ref);
+        if (b.unres) return EM_PENDING;
+        if (o.o) {
+          const uint32_t open = b.mode == BOX_MAP ? '{' : b.mode == BOX_ARRAY ? '[' : '"';
+          const uint32_t close = b.mode == BOX_MAP ? '}' : b.mode == BOX_ARRAY ? ']' : '"';
+          JText t{o.o, o.n, o.cap};
+          t.ch(open);
+          t.n = o.n + b.size - 1;
+          t.ch(close);
         }
-        sep();
+        o.n += b.size;
+        break;
       }
-      return EM_OK;
-    case R_JSON:
-      for (uint32_t i = 0; i < n; ++i) {
-        const uint32_t k = r.vu();
-        const uint8_t* q = r.take(k);
-        if (!r.ok) return EM_REFUSED;
-        const char* u = "undefined";
-        bool undef = k == 9;
-        for (uint32_t j = 0; undef && j < 9; ++j) undef = q[j] == (uint8_t)u[j];
-        if (undef) {
-          if (entry) return EM_OMIT;
-          o.lit("null");
-        } else {
-          o.raw(q, k);
-        }
-        sep();
-      }
-      return EM_OK;
-    case R_STRING: {  // one element per character
-      uint64_t p = s.b0;
-      if (entry) {
-        if (p >= s.b1) return EM_OMIT;
-        uint64_t last = p;
-        while (p < s.b1) { last = p; p += utf8_len(a.bytes[p]); }
-        json_put_str(o, a.bytes + last, s.b1 - last);
-        return EM_OK;
-      }
-      while (p < s.b1) {
-        const uint64_t l = min((uint64_t)utf8_len(a.bytes[p]), s.b1 - p);
-        json_put_str(o, a.bytes + p, l);
-        sep();
-        p += l;
-      }
-      return EM_OK;
+      default: return EM_REFUSED;  // EL_BAD, EL_DEEP
     }
-    case R_BINARY: {
-      const uint32_t k = r.vu();
-      const uint8_t* q = r.take(k);
-      if (!r.ok) return EM_REFUSED;
-      json_put_bytes(o, q, k);
-      sep();
-      return EM_OK;
-    }
-    case R_EMBED: {
-      const uint32_t k = r.vu();
-      const uint8_t* q = r.take(k);
-      if (!r.ok) return EM_REFUSED;
-      o.raw(q, k);
-      sep();
-      return EM_OK;
-    }
-    case R_TYPE: {
-      const uint32_t tr = r.vu();
-      if (!r.ok) return EM_REFUSED;
-      if (!scans) return EM_PENDING;
-      const Box b = type_box(a, s.unit + s.len - 1, tr);
-      if (b.unres) return EM_PENDING;
-      if (o.o) {
-        const uint32_t open = b.mode == BOX_MAP ? '{' : b.mode == BOX_ARRAY ? '[' : '"';
-        const uint32_t close = b.mode == BOX_MAP ? '}' : b.mode == BOX_ARRAY ? ']' : '"';
-        JText c{o.o, o.n, o.cap};
-        c.ch(open);
-        c.n = o.n + b.size - 1;
-        c.ch(close);
-      }
-      o.n += b.size;
-      sep();
-      return EM_OK;
-    }
-    case R_FORMAT:
-      if (entry) return EM_OMIT;
-      return EM_OK;  // (not countable: never asked)
-    default:
-      o.lit("null");
-      sep();
-      return EM_OK;
+    if (entry) return EM_OK;
+    if (!o.o || o.n != cend) o.ch(',');
   }
 }
 
@@ -318,7 +246,7 @@ __global__ void k_jsize(JsonArgs a, uint32_t round) {
     const ViewSeg& s = a.segs[i - a.ck];
     if (round == 0) {  // what the segment adds to a YText: its escaped string, no quotes
       uint32_t t = 0;
-      if (!(s.flags & VS_DELETED) && (s.flags & VS_ITEM) && s.ref == R_STRING && s.b0 <= s.b1 && s.b1 <= a.nbytes) {
+      if (!(s.flags & VS_DELETED) && (s.flags & VS_ITEM) && s.ref == REF_STRING && s.b0 <= s.b1 && s.b1 <= a.nbytes) {
         JText q{nullptr, 0};
         json_put_esc(q, a.bytes + s.b0, s.b1 - s.b0);
         t = q.n > 0xFFFFFFF0ull ? 0u : (uint32_t)q.n;
@@ -441,7 +369,7 @@ __global__ void k_jplace(JsonArgs a) {
   }
   a.cend[i] = end;
   a.apos[i] = at;
-  if (sg->ref != R_TYPE) return;
+  if (sg->ref != REF_TYPE) return;
   JRd r{a.bytes, sg->b0, sg->b1, true};
   const uint32_t tr = r.vu();
   if (!r.ok) return;

@@ -1340,8 +1340,7 @@ YC_HD inline __attribute__((noinline)) uint32_t any_content_canon(const uint8_t*
               }
               continue;
             }
-            uint32_t h = 2166136261u;
-            for (uint32_t i = 0; i < kl; ++i) h = (h ^ b[ks + i]) * 16777619u;
+            const uint32_t h = fnv_key(b, ks, kl);
             bool dup = false;
             for (uint32_t i = 0; i < k && !dup; ++i) {
               uint32_t* r = mem(f, i);

@@ -2,8 +2,9 @@
 kernels) against Node: tests/golden/any_json.json (tests/golden/gen/gen_any_json_fixtures.js) holds
 hand-encoded and seeded `any` values with JSON.stringify of what Yjs 13.5.16 reads from them. The
 host build of the function (tests/csrc/any_json_main.cpp) must give Node's text byte for byte, the
-size-only pass must report exactly the bytes the write pass writes, a value nested past the 64-level
-stack and every truncated value must be refused. BigInt64 (JSON.stringify throws) is pinned against
+size-only pass must report exactly the bytes the write pass writes, the string sink of the host must
+receive the bytes the device sink does, a value nested past the stack it is given (64 levels on the
+device, 4000 on the host) and every truncated value must be refused. BigInt64 (JSON.stringify throws) is pinned against
 Python's str(int). The same program is built a second time with AddressSanitizer and UBSan: inputs
 and outputs sit in heap blocks of their exact size, so a read past a truncated value or a write
 past the reported size aborts the run."""
@@ -66,6 +67,34 @@ def _check(out, fx):
         assert f[0] == "T" and int(f[1]) == nbytes and int(f[2]) == nbytes, (n, line)  # every strict prefix refused
 
 
+def _nest(n):
+    """n containers, arrays and objects alternating, one member each, 0 at the bottom: (any as hex, text)"""
+    enc = "".join("7501" if i % 2 == 0 else "7601016b" for i in range(n)) + "7d00"
+    text = "".join("[" if i % 2 == 0 else '{"k":' for i in range(n)) + "0" + "".join("]" if i % 2 == 0 else "}" for i in reversed(range(n)))
+    return enc, text
+
+
+def _check_depths(exe):
+    depths = (64, 65, 100, 2000, 4000, 4001)
+    lines = [f"{m} {_nest(n)[0]}" for n in depths for m in "VH"]
+    r = subprocess.run([str(exe)], input="\n".join(lines) + "\n", capture_output=True, text=True)
+    assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
+    out = [x.split(" ") for x in r.stdout.splitlines()]
+    assert len(out) == len(lines)
+    for k, n in enumerate(depths):
+        enc, text = _nest(n)
+        dev, host = out[2 * k], out[2 * k + 1]
+        assert dev[0] == "V" and host[0] == "H", n
+        if n <= 64:  # the 64-level stack
+            assert int(dev[1]) == AJ_OK and int(dev[4]) == len(enc) // 2 and bytes.fromhex(dev[5]).decode() == text, n
+        else:
+            assert int(dev[1]) == AJ_DEEP, (n, dev[:2])
+        if n <= 4000:  # the 4000-level stack
+            assert int(host[1]) == AJ_OK and int(host[2]) == len(enc) // 2 and bytes.fromhex(host[3]).decode() == text, n
+        else:
+            assert int(host[1]) == AJ_DEEP, (n, host[:2])
+
+
 def test_fixture_covers_the_forms():
     fx = _fixture()
     names = {c["name"] for c in fx["cases"]}
@@ -86,7 +115,9 @@ def test_fixture_covers_the_forms():
 
 def test_any_json_text_matches_node(tmp_path):
     fx = _fixture()
-    _check(_run(_build(tmp_path, "any_json", []), fx), fx)
+    exe = _build(tmp_path, "any_json", [])
+    _check(_run(exe, fx), fx)
+    _check_depths(exe)
 
 
 def test_any_json_text_sanitized(tmp_path):
@@ -96,6 +127,7 @@ def test_any_json_text_sanitized(tmp_path):
     except subprocess.CalledProcessError:
         pytest.fail("the sanitizer build of tests/csrc/any_json_main.cpp failed")
     _check(_run(exe, fx), fx)
+    _check_depths(exe)
 
 
 def test_docs_json_abi_without_a_device():
