@@ -137,6 +137,11 @@ inline bool env_off(const char* name) {
   const char* v = getenv(name);
   return v && v[0] == '0';
 }
+// a host switch set to 1 (paths that are off by default)
+inline bool env_on(const char* name) {
+  const char* v = getenv(name);
+  return v && v[0] == '1';
+}
 
 __device__ __forceinline__ void raise_err(uint32_t* err, uint32_t code) {
   atomicCAS(err, 0u, code);

@@ -1,5 +1,9 @@
 // yc_engine.hip — host orchestration of the batched merge + the C ABI (include/ycrdt.h).
 //
+// One translation unit, in this order: buffers and the arena, batch staging, the device passes over a
+// staged batch (decode, merge, view, lazy merge / diff, the per-document split), the doc model, the
+// calls over many documents, the batch and comm ABI, local ops and reads. The helpers that make no HIP call are in yc_engine_host.h (tested on the CPU).
+//
 // One engine = one HIP device + one stream + a grow-only set of HBM buffers. A merge runs the
 // decode → dedupe → delete-set → segmentation → map-winner → encode kernels back to back on the
 // engine stream; the host only reads a handful of counters at the sync points where the next
@@ -24,6 +28,7 @@
 #include <thread>
 #include <atomic>
 #include "../../include/ycrdt.h"
+#include "yc_engine_host.h"
 
 using namespace yc;
 
@@ -144,57 +149,6 @@ uint32_t next_pow2(uint64_t v) {
   uint64_t p = 1;
   while (p < v) p <<= 1;
   return (uint32_t)std::min<uint64_t>(p, 1ull << 31);
-}
-
-// decode a state vector (varuint n, (client, clock) × n): put(client, clock) per entry
-template <class Put>
-bool parse_sv_each(const uint8_t* p, size_t n, Put put) {
-  size_t pos = 0;
-  auto vu = [&](uint32_t& v) -> bool {
-    uint32_t r = 0;
-    int shift = 0;
-    for (;;) {
-      if (pos >= n) return false;
-      uint32_t b = p[pos++];
-      if (shift < 32) r |= (b & 0x7fu) << shift;
-      shift += 7;
-      if (b < 0x80) { v = r; return true; }
-      if (shift > 35) return false;
-    }
-  };
-  uint32_t k;
-  if (!vu(k)) return false;
-  for (uint32_t i = 0; i < k; ++i) {
-    uint32_t c, cl;
-    if (!vu(c) || !vu(cl)) return false;
-    put(c, cl);
-  }
-  return true;
-}
-bool parse_sv(const uint8_t* p, size_t n, std::unordered_map<uint32_t, uint32_t>& out) {
-  return parse_sv_each(p, n, [&](uint32_t c, uint32_t cl) { out[c] = cl; });
-}
-// the same as (client, clock) pairs with the clients ascending (a client named twice: its last
-// clock, as the map gives). Yjs writes state vectors in descending or store order: no hashing,
-// and no sort when the input is already in either order.
-bool parse_sv_sorted(const uint8_t* p, size_t n, std::vector<std::pair<uint32_t, uint32_t>>& v) {
-  v.clear();
-  if (!parse_sv_each(p, n, [&](uint32_t c, uint32_t cl) { v.emplace_back(c, cl); })) return false;
-  auto before = [](const std::pair<uint32_t, uint32_t>& a, const std::pair<uint32_t, uint32_t>& b) { return a.first < b.first; };
-  auto after = [](const std::pair<uint32_t, uint32_t>& a, const std::pair<uint32_t, uint32_t>& b) { return a.first > b.first; };
-  if (std::adjacent_find(v.begin(), v.end(), [&](const auto& a, const auto& b) { return !before(a, b); }) == v.end()) return true;
-  if (std::adjacent_find(v.begin(), v.end(), [&](const auto& a, const auto& b) { return !after(a, b); }) == v.end()) {
-    std::reverse(v.begin(), v.end());
-    return true;
-  }
-  std::stable_sort(v.begin(), v.end(), before);
-  size_t w = 0;
-  for (size_t i = 0; i < v.size(); ++i) {
-    if (i + 1 < v.size() && v[i + 1].first == v[i].first) continue;  // (the last of equal clients wins)
-    v[w++] = v[i];
-  }
-  v.resize(w);
-  return true;
 }
 
 enum Buf {
@@ -381,6 +335,16 @@ void mark(ycrdt_engine* e, const char* name) {
   hipEvent_t ev = e->event_pool[e->marks.size()];
   hipEventRecord(ev, e->stream);
   e->marks.push_back({name, ev});
+}
+// the times between this pass's phase marks into e->phase_ms (profiling engines; the marks' events
+// must have completed)
+void collect_phase_ms(ycrdt_engine* e) {
+  if (!e->profiling) return;
+  for (size_t i = 0; i + 1 < e->marks.size(); ++i) {
+    float t = 0;
+    hipEventElapsedTime(&t, e->marks[i].second, e->marks[i + 1].second);
+    e->phase_ms.push_back({e->marks[i].first, (double)t});
+  }
 }
 
 // Small updates are parsed directly, one lane per update walking its structs exactly, when there
@@ -1683,23 +1647,20 @@ int run_merge(ycrdt_engine* e, ycrdt_batch* b, const std::unordered_map<uint32_t
   return YCRDT_OK;
 }
 
-// K8: materialised view of the doc state just merged into the engine's workspace (yc_view.hip),
-// copied to the host with the state bytes its byte ranges point into.
-int run_view(ycrdt_engine* e, ycrdt_batch* b, HostView& hv) {
-  if (b->nwin > 1) return fail(YCRDT_E_CAPACITY, "a view of a batch over 4 GiB");
+// the view kernels' buffers over the merge in the workspace (its lists numbered first when the merge
+// skipped that); narr: the members of its YArray lists, read back (the one synchronisation in here)
+int view_workspace(ycrdt_engine* e, uint32_t nsegs, ViewBufs& vb, uint32_t& narr) {
   Work& w = e->w;
   auto& V = e->bufs;
   g_bufs = &V;
   bool ok = true;
   hipStream_t s = e->stream;
-  if (e->nlists == LISTS_UNNUMBERED) e->nlists = launch_ylists(w, e->nsegs, s);  // (the merge's tree path skipped it)
-  const uint32_t nsegs = e->nsegs, nlists = e->nlists;
-  uint32_t narr = 0;
-  if (nlists) {
-    HIPCHK(hipMemcpyAsync(&narr, w.y_lstart + nlists, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  if (e->nlists == LISTS_UNNUMBERED) e->nlists = launch_ylists(w, nsegs, s);  // (the merge's tree path skipped it)
+  narr = 0;
+  if (e->nlists) {
+    HIPCHK(hipMemcpyAsync(&narr, w.y_lstart + e->nlists, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
   }
-  ViewBufs vb;
   const size_t ck = std::max<uint32_t>(w.cap_keys, 1);
   vb.kmap = take<uint32_t>(V, B_VKMAP, ck, ok);
   vb.krep = take<uint32_t>(V, B_VKREP, ck, ok);
@@ -1713,6 +1674,21 @@ int run_view(ycrdt_engine* e, ycrdt_batch* b, HostView& hv) {
   vb.order = take<uint32_t>(V, B_VORDER, (size_t)narr + 1, ok);
   vb.segs = take<ViewSeg>(V, B_VSEGS, (size_t)narr + 1, ok);
   if (!ok) return fail(YCRDT_E_DEVICE, oom("view"));
+  return YCRDT_OK;
+}
+
+// K8: materialised view of the doc state just merged into the engine's workspace (yc_view.hip),
+// copied to the host with the state bytes its byte ranges point into.
+int run_view(ycrdt_engine* e, ycrdt_batch* b, HostView& hv) {
+  if (b->nwin > 1) return fail(YCRDT_E_CAPACITY, "a view of a batch over 4 GiB");
+  Work& w = e->w;
+  hipStream_t s = e->stream;
+  const uint32_t nsegs = e->nsegs;
+  ViewBufs vb;
+  uint32_t narr = 0;
+  if (const int rc = view_workspace(e, nsegs, vb, narr)) return rc;
+  const uint32_t nlists = e->nlists;
+  const size_t ck = std::max<uint32_t>(w.cap_keys, 1);
   hv.keys.clear();
   hv.segs.clear();
   hv.bytes.assign(b->nbytes, 0);
@@ -1721,7 +1697,7 @@ int run_view(ycrdt_engine* e, ycrdt_batch* b, HostView& hv) {
     // a small view (the per-op path's doc) comes back in ONE synchronisation: counters, key count,
     // the key table up to its capacity, the list segments and the state bytes, queued together
     // (each synchronous copy cost a ~25 us round trip); a large one sizes the key copy first
-    static const bool big_only = getenv("YCRDT_VIEW_SYNC") && getenv("YCRDT_VIEW_SYNC")[0] == '1';
+    static const bool big_only = env_on("YCRDT_VIEW_SYNC");
     const bool small = !big_only && (uint64_t)ck * sizeof(ViewKey) <= (256u << 10);
     Counters c;
     uint32_t nkeys = 0;
@@ -1979,13 +1955,7 @@ int run_lazy(ycrdt_engine* e, ycrdt_batch* b, bool merge, const std::vector<std:
   HIPCHK(hipEventRecord(e->ev1, s));
   rc = check(e, c, "lazy write");
   if (rc) return rc;
-  if (e->profiling) {  // phase times of the lazy pipeline (stage .. last kernel, host syncs included)
-    for (size_t i = 0; i + 1 < e->marks.size(); ++i) {
-      float t = 0;
-      hipEventElapsedTime(&t, e->marks[i].second, e->marks[i + 1].second);
-      e->phase_ms.push_back({e->marks[i].first, (double)t});
-    }
-  }
+  collect_phase_ms(e);  // phase times of the lazy pipeline (stage .. last kernel, host syncs included)
   if (multi) return split_multi(e, D, nr, sbytes, total, multi);
   out->len = total;
   out->ptr = (uint8_t*)malloc(total ? total : 1);
@@ -2133,12 +2103,13 @@ int split_docs(ycrdt_engine* e, ycrdt_batch* b, ycrdt_out* outs, ycrdt_out* svs)
   return YCRDT_OK;
 }
 
-int empty_update(ycrdt_out* out) {
-  out->ptr = (uint8_t*)malloc(2);
+// `len` bytes of p as a ycrdt_out the caller releases with ycrdt_free (one byte is allocated for an
+// empty result, so ptr is never null on success)
+int out_set(ycrdt_out* out, const void* p, size_t len) {
+  out->ptr = (uint8_t*)malloc(len ? len : 1);
   if (!out->ptr) { out->len = 0; return fail(YCRDT_E_CAPACITY, "host allocation failed"); }
-  out->ptr[0] = 0;
-  out->ptr[1] = 0;
-  out->len = 2;
+  out->len = len;
+  if (len) memcpy(out->ptr, p, len);
   return YCRDT_OK;
 }
 
@@ -2165,7 +2136,7 @@ int ycrdt_engine_create(int device, int compat, ycrdt_engine** out) {
   auto* e = new ycrdt_engine();
   e->device = device;
   e->compat = compat == 135 ? 135 : 136;
-  e->debug_sync = getenv("YCRDT_DEBUG_SYNC") && getenv("YCRDT_DEBUG_SYNC")[0] == '1';
+  e->debug_sync = env_on("YCRDT_DEBUG_SYNC");
   if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) { delete e; return fail(YCRDT_E_DEVICE, "stream"); }
   if (hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking) != hipSuccess) { delete e; return fail(YCRDT_E_DEVICE, "stream"); }
   hipEventCreateWithFlags(&e->side_done, hipEventDisableTiming);
@@ -2293,22 +2264,34 @@ int predecode_mode() {
   const char* v = getenv("YCRDT_PREDECODE");
   return v && v[0] == '0' ? 0 : v && !strcmp(v, "check") ? 2 : 1;
 }
+
+// the marks block at p (yc_engine_host.h marks_layout: the one definition of its byte layout)
+static_assert(sizeof(Section) == 32, "tests/test_engine_host.py checks the marks layout with this size");
+PreMarks pre_marks(void* p, uint32_t nw, uint32_t cap) {
+  const MarksLayout at = marks_layout(nw, cap, sizeof(Section));
+  uint8_t* m = (uint8_t*)p;
+  PreMarks pm;
+  pm.fbits = (uint64_t*)m;
+  pm.sbits = (uint64_t*)(m + at.sbits);
+  pm.secs = (Section*)(m + at.secs);
+  pm.meta = (uint32_t*)(m + at.meta);
+  pm.nw = nw;
+  pm.cap_secs = cap;
+  return pm;
+}
+// the marks describe the doc's current state
+bool marked(const ycrdt_doc* d) { return d->marks.p && d->marks_len == d->state_len && d->marks_cap > 0; }
 // the doc's state goes into the next batch as source 0: decoded from its marks when they describe it
 void doc_pre(ycrdt_doc* d, ycrdt_batch& b) {
   b.pre_src = -1;
   b.pre_check = false;
   const int mode = predecode_mode();
   if (!mode || !d->state_len || d->marks_len != d->state_len || !d->marks.p) return;
-  uint8_t* m = (uint8_t*)d->marks.p;
-  b.pre.fbits = (uint64_t*)m;
-  b.pre.sbits = (uint64_t*)(m + 8ull * d->marks_nw);
-  b.pre.secs = (Section*)(m + 16ull * d->marks_nw);
-  b.pre.meta = (uint32_t*)(m + 16ull * d->marks_nw + sizeof(Section) * d->marks_cap);
-  b.pre.nw = d->marks_nw;
-  b.pre.cap_secs = d->marks_cap;
+  b.pre = pre_marks(d->marks.p, d->marks_nw, d->marks_cap);
   b.pre_src = 0;
   b.pre_check = mode == 2;
 }
+
 // after a successful merge of the doc (the workspace holds its encode): the marks of the new state
 void doc_marks(ycrdt_doc* d) {
   ycrdt_engine* e = d->e;
@@ -2316,24 +2299,14 @@ void doc_marks(ycrdt_doc* d) {
   if (!predecode_mode() || !e->out_bytes || e->out_bytes >= (uint64_t(1) << 31)) return;
   // (exactly the state's own 64-byte slot: the next staged update's words follow it)
   const uint32_t nw = (uint32_t)((e->out_bytes + 63) / 64), cap = (uint32_t)e->last.clients + 1;
-  const size_t bytes = 16ull * nw + sizeof(Section) * cap + 16;
+  const size_t bytes = marks_layout(nw, cap, sizeof(Section)).bytes;
   if (d->marks.cap < bytes) {
     release_state(e, d->marks);
     if (!alloc_state(e, d->marks, bytes)) { (void)hipGetLastError(); d->marks = DevBuf(); return; }
   }
   d->marks_nw = nw;
   d->marks_cap = cap;
-  {
-    uint8_t* m = (uint8_t*)d->marks.p;
-    PreMarks pm;
-    pm.fbits = (uint64_t*)m;
-    pm.sbits = (uint64_t*)(m + 8ull * nw);
-    pm.secs = (Section*)(m + 16ull * nw);
-    pm.meta = (uint32_t*)(m + 16ull * nw + sizeof(Section) * cap);
-    pm.nw = nw;
-    pm.cap_secs = cap;
-    launch_state_marks(e->w, (uint32_t)e->last.out_structs, (uint32_t)e->last.clients, pm, e->stream);
-  }
+  launch_state_marks(e->w, (uint32_t)e->last.out_structs, (uint32_t)e->last.clients, pre_marks(d->marks.p, nw, cap), e->stream);
   d->marks_len = e->out_bytes;
 }
 
@@ -2370,7 +2343,7 @@ int commit_merge(ycrdt_doc* d, const std::vector<ycrdt_buf>& extra, const ClockM
     folded = true;
     return YCRDT_OK;
   };
-  static const bool nofold = getenv("YCRDT_NO_FOLD") && getenv("YCRDT_NO_FOLD")[0] == '1';  // (A/B)
+  static const bool nofold = env_on("YCRDT_NO_FOLD");  // (A/B)
   if (rc == YCRDT_OK) {
     e->before_final = nofold ? nullptr : &fold;
     rc = run_merge(e, &b, nullptr, caps, order);
@@ -2605,6 +2578,58 @@ int flush_multi(ycrdt_engine* e, const std::vector<ycrdt_doc*>& docs) {
   return YCRDT_OK;
 }
 
+// Y.applyUpdate's validation of n updates: scans[i] and ok[i] of every one (threads for large input)
+void validate_updates(const ycrdt_buf* ups, size_t n, std::vector<UpdScan>& scans, std::vector<char>& ok) {
+  scans.resize(n);
+  ok.assign(n, 0);
+  size_t total = 0;
+  for (size_t i = 0; i < n; ++i) total += ups[i].len;
+  const size_t nt = total > (size_t(4) << 20) && n > 1 ? std::min<size_t>({n, 16, std::max(1u, std::thread::hardware_concurrency())}) : 1;
+  auto work = [&](size_t t) {
+    for (size_t i = t; i < n; i += nt) ok[i] = scan_update(ups[i].ptr, ups[i].len, false, scans[i]) ? 1 : 0;
+  };
+  if (nt > 1) {
+    std::vector<std::thread> th;
+    for (size_t t = 0; t < nt; ++t) th.emplace_back(work, t);
+    for (auto& t : th) t.join();
+  } else {
+    work(0);
+  }
+}
+
+// update i did not validate: the code and text Y.applyUpdate's throw maps to; what Yjs integrates
+// before it throws is queued on d
+int refuse_update(ycrdt_doc* d, const ycrdt_buf& up, size_t i, const UpdScan& sc, std::string& err) {
+  if (sc.unsupported) {
+    err = "update " + std::to_string(i) + ": an any value nests deeper than 32 levels (engine limit)";
+    return YCRDT_E_UNSUPPORTED;
+  }
+  // Yjs integrates a well-formed struct section and the delete-set ranges read before the error
+  if (sc.structs_ok) {
+    const std::vector<uint8_t> r = repaired_update(up.ptr, sc);
+    enqueue(d, r.data(), r.size(), false, true);
+  }
+  err = "Integer out of range! (malformed update " + std::to_string(i) + ")";
+  return YCRDT_E_DECODE;
+}
+
+// ---- helpers of the calls over many documents
+
+int check_docs(ycrdt_engine* e, ycrdt_doc* const* docs, size_t n) {
+  for (size_t i = 0; i < n; ++i)
+    if (!docs[i] || docs[i]->e != e) return fail(YCRDT_E_ARG, "document of another engine (or null) at " + std::to_string(i));
+  return YCRDT_OK;
+}
+
+// the queued applies of docs[0 .. n) merged now: every such document once, in one pass (flush_multi)
+int flush_queued(ycrdt_engine* e, ycrdt_doc* const* docs, size_t n) {
+  std::vector<ycrdt_doc*> q;
+  for (size_t i = 0; i < n; ++i) if (!docs[i]->queue.empty()) q.push_back(docs[i]);
+  std::sort(q.begin(), q.end());
+  q.erase(std::unique(q.begin(), q.end()), q.end());
+  return flush_multi(e, q);
+}
+
 }  // namespace
 
 extern "C" {
@@ -2614,32 +2639,13 @@ extern "C" {
 int ycrdt_apply_updates(ycrdt_doc* d, const ycrdt_buf* ups, size_t n) {
   if (!d || (!ups && n)) return fail(YCRDT_E_ARG, "null arg");
   if (n == 0) return YCRDT_OK;
-  std::vector<UpdScan> sc(n);
-  std::vector<char> ok(n, 0);
-  size_t total = 0;
-  for (size_t i = 0; i < n; ++i) total += ups[i].len;
-  const size_t nt = total > (size_t(4) << 20) && n > 1 ? std::min<size_t>({n, 16, std::max(1u, std::thread::hardware_concurrency())}) : 1;
-  auto work = [&](size_t t) {
-    for (size_t i = t; i < n; i += nt) ok[i] = scan_update(ups[i].ptr, ups[i].len, false, sc[i]) ? 1 : 0;
-  };
-  if (nt > 1) {
-    std::vector<std::thread> th;
-    for (size_t t = 0; t < nt; ++t) th.emplace_back(work, t);
-    for (auto& t : th) t.join();
-  } else {
-    work(0);
-  }
+  std::vector<UpdScan> sc;
+  std::vector<char> ok;
+  validate_updates(ups, n, sc, ok);
+  std::string err;
   for (size_t i = 0; i < n; ++i) {
-    if (!ok[i] && sc[i].unsupported)
-      return fail(YCRDT_E_UNSUPPORTED, "update " + std::to_string(i) + ": an any value nests deeper than 32 levels (engine limit)");
-    if (!ok[i]) {
-      // Yjs integrates a well-formed struct section and the delete-set ranges read before the error
-      if (sc[i].structs_ok) {
-        const std::vector<uint8_t> r = repaired_update(ups[i].ptr, sc[i]);
-        enqueue(d, r.data(), r.size(), false, true);
-      }
-      return fail(YCRDT_E_DECODE, "Integer out of range! (malformed update " + std::to_string(i) + ")");
-    }
+    if (!ok[i]) return fail(refuse_update(d, ups[i], i, sc[i], err), err);
+    // (the scan's struct / section counts are decode hints: a large update of few structs needs no chunk walk)
     enqueue(d, ups[i].ptr, ups[i].len, false, false, (int32_t)std::min<uint64_t>(sc[i].nstructs, 0x7FFFFFFF), (int32_t)sc[i].secs.size());
   }
   if (d->queue_bytes > QUEUE_FLUSH_BYTES) return flush(d);
@@ -2653,48 +2659,19 @@ int ycrdt_apply_update(ycrdt_doc* d, ycrdt_buf update) { return ycrdt_apply_upda
 // for every document on the fast path (flush_multi).
 int ycrdt_apply_updates_multi(ycrdt_engine* e, ycrdt_doc* const* docs, const ycrdt_buf* ups, size_t n) {
   if (!e || (n && (!docs || !ups))) return fail(YCRDT_E_ARG, "null arg");
-  for (size_t i = 0; i < n; ++i)
-    if (!docs[i] || docs[i]->e != e) return fail(YCRDT_E_ARG, "document of another engine (or null) at " + std::to_string(i));
-  std::vector<UpdScan> sc(n);
-  std::vector<char> ok(n, 0);
-  size_t total = 0;
-  for (size_t i = 0; i < n; ++i) total += ups[i].len;
-  const size_t nt = total > (size_t(4) << 20) && n > 1 ? std::min<size_t>({n, 16, std::max(1u, std::thread::hardware_concurrency())}) : 1;
-  auto work = [&](size_t t) {
-    for (size_t i = t; i < n; i += nt) ok[i] = scan_update(ups[i].ptr, ups[i].len, false, sc[i]) ? 1 : 0;
-  };
-  if (nt > 1) {
-    std::vector<std::thread> th;
-    for (size_t t = 0; t < nt; ++t) th.emplace_back(work, t);
-    for (auto& t : th) t.join();
-  } else {
-    work(0);
-  }
-  std::vector<ycrdt_doc*> touched;
+  if (const int rc = check_docs(e, docs, n)) return rc;
+  std::vector<UpdScan> sc;
+  std::vector<char> ok;
+  validate_updates(ups, n, sc, ok);
+  // sequential semantics: what came before a refused update is applied, then Yjs throws
   int rc = YCRDT_OK;
   std::string err;
-  for (size_t i = 0; i < n; ++i) {
-    ycrdt_doc* d = docs[i];
-    touched.push_back(d);
-    if (!ok[i] && sc[i].unsupported) {  // the earlier updates are applied; this one is refused
-      rc = YCRDT_E_UNSUPPORTED;
-      err = "update " + std::to_string(i) + ": an any value nests deeper than 32 levels (engine limit)";
-      break;
-    }
-    if (!ok[i]) {  // sequential semantics: what came before is applied, then Yjs throws
-      if (sc[i].structs_ok) {
-        const std::vector<uint8_t> r = repaired_update(ups[i].ptr, sc[i]);
-        enqueue(d, r.data(), r.size(), false, true);
-      }
-      rc = YCRDT_E_DECODE;
-      err = "Integer out of range! (malformed update " + std::to_string(i) + ")";
-      break;
-    }
-    enqueue(d, ups[i].ptr, ups[i].len, false);
+  size_t seen = 0;
+  for (; seen < n && !rc; ++seen) {
+    if (!ok[seen]) rc = refuse_update(docs[seen], ups[seen], seen, sc[seen], err);
+    else enqueue(docs[seen], ups[seen].ptr, ups[seen].len, false);  // (without the scan's counts as decode hints: DESIGN.md §6b, host layer)
   }
-  std::sort(touched.begin(), touched.end());
-  touched.erase(std::unique(touched.begin(), touched.end()), touched.end());
-  const int frc = flush_multi(e, touched);
+  const int frc = flush_queued(e, docs, seen);
   if (rc) return fail(rc, err);
   return frc;
 }
@@ -2706,16 +2683,9 @@ int ycrdt_apply_updates_multi(ycrdt_engine* e, ycrdt_doc* const* docs, const ycr
 int ycrdt_docs_states_packed(ycrdt_engine* e, ycrdt_doc* const* docs, size_t n, uint8_t* dst, uint64_t cap, uint64_t* offs,
                              uint64_t* total) {
   if (!e || (n && !docs)) return fail(YCRDT_E_ARG, "null arg");
-  for (size_t i = 0; i < n; ++i)
-    if (!docs[i] || docs[i]->e != e) return fail(YCRDT_E_ARG, "document of another engine (or null) at " + std::to_string(i));
+  if (const int rc = check_docs(e, docs, n)) return rc;
   HIPCHK(hipSetDevice(e->device));
-  {
-    std::vector<ycrdt_doc*> q;
-    for (size_t i = 0; i < n; ++i) if (!docs[i]->queue.empty()) q.push_back(docs[i]);
-    std::sort(q.begin(), q.end());
-    q.erase(std::unique(q.begin(), q.end()), q.end());
-    if (const int rc = flush_multi(e, q)) return rc;
-  }
+  if (const int rc = flush_queued(e, docs, n)) return rc;
   std::vector<uint64_t> o(2 * n + 1, 0);
   std::vector<std::vector<uint8_t>> slow(n);  // pending documents: their encode (host)
   uint64_t pos = 0;
@@ -2785,10 +2755,9 @@ constexpr uint32_t SYNC_WALK_MAX = 65536;  // a mark-less state up to this many 
 int ycrdt_docs_diff(ycrdt_engine* e, ycrdt_doc* const* docs, const ycrdt_buf* svs, size_t n, ycrdt_out* blob, uint64_t* offs,
                     ycrdt_sync_stats* st) {
   if (!e || !docs || !blob || !offs || (n && !svs)) return fail(YCRDT_E_ARG, "null arg");
-  for (size_t i = 0; i < n; ++i) {
-    if (!docs[i] || docs[i]->e != e) return fail(YCRDT_E_ARG, "document of another engine (or null) at " + std::to_string(i));
+  if (const int rc = check_docs(e, docs, n)) return rc;
+  for (size_t i = 0; i < n; ++i)
     if (svs[i].len && !svs[i].ptr) return fail(YCRDT_E_ARG, "null state vector at " + std::to_string(i));
-  }
   blob->ptr = nullptr;
   blob->len = 0;
   offs[0] = 0;
@@ -2816,18 +2785,11 @@ int ycrdt_docs_diff(ycrdt_engine* e, ycrdt_doc* const* docs, const ycrdt_buf* sv
     sv_off[i + 1] = (uint32_t)svk.size();
   }
   HIPCHK(hipSetDevice(e->device));
-  {
-    std::vector<ycrdt_doc*> q;
-    for (size_t i = 0; i < n; ++i) if (!docs[i]->queue.empty()) q.push_back(docs[i]);
-    std::sort(q.begin(), q.end());
-    q.erase(std::unique(q.begin(), q.end()), q.end());
-    if (const int rc = flush_multi(e, q)) return rc;
-  }
+  if (const int rc = flush_queued(e, docs, n)) return rc;
   // which path every pair takes
   enum : uint8_t { K_SINGLE = 0, K_EMPTY, K_DEV };
   const bool off = env_off("YCRDT_SYNC");
   std::vector<uint8_t> kind(n, K_SINGLE);
-  auto marked = [](const ycrdt_doc* d) { return d->marks.p && d->marks_len == d->state_len && d->marks_cap > 0; };
   size_t ndev = 0;
   for (size_t i = 0; i < n; ++i) {
     const ycrdt_doc* d = docs[i];
@@ -2880,10 +2842,10 @@ int ycrdt_docs_diff(ycrdt_engine* e, ycrdt_doc* const* docs, const ycrdt_buf* sv
         add_sv(m);
         if (svk.size() >= 0xFFFFFFF0ull) return fail(YCRDT_E_CAPACITY, "state vectors too large");
         if (marked(d)) {
-          const uint8_t* mk = (const uint8_t*)d->marks.p;
-          D.fbits = (const uint64_t*)mk;
-          D.secs = (const Section*)(mk + 16ull * d->marks_nw);
-          D.meta = (const uint32_t*)(mk + 16ull * d->marks_nw + sizeof(Section) * d->marks_cap);
+          const PreMarks pm = pre_marks(d->marks.p, d->marks_nw, d->marks_cap);
+          D.fbits = pm.fbits;
+          D.secs = pm.secs;
+          D.meta = pm.meta;
           D.nslots = d->marks_cap - 1;
         } else {  // (pointers below, once the workspace is laid out)
           D.nslots = (uint32_t)m.size();
@@ -3013,14 +2975,8 @@ int ycrdt_docs_diff(ycrdt_engine* e, ycrdt_doc* const* docs, const ycrdt_buf* sv
     hipEventElapsedTime(&ms, e->ev0, e->ev1);
     S.device_ms = ms;
     S.cut_structs = c.cut_structs;
-    if (e->profiling) {
-      HIPCHK(hipStreamSynchronize(s));
-      for (size_t i = 0; i + 1 < e->marks.size(); ++i) {
-        float t = 0;
-        hipEventElapsedTime(&t, e->marks[i].second, e->marks[i + 1].second);
-        e->phase_ms.push_back({e->marks[i].first, (double)t});
-      }
-    }
+    if (e->profiling) HIPCHK(hipStreamSynchronize(s));
+    collect_phase_ms(e);
     if (direct) {
       blob->ptr = dst;
       blob->len = total;
@@ -3105,28 +3061,13 @@ int json_pass(ycrdt_engine* e, const std::vector<ycrdt_doc*>& dl, const std::vec
   g_bufs = &V;
   bool ok = true;
   hipStream_t s = e->stream;
-  if (e->nlists == LISTS_UNNUMBERED) e->nlists = launch_ylists(w, e->nsegs, s);
-  const uint32_t nsegs = e->nsegs, nlists = e->nlists;
-  if (!nsegs) return refuse_all();
-  uint32_t narr = 0;
-  if (nlists) {
-    HIPCHK(hipMemcpyAsync(&narr, w.y_lstart + nlists, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-  }
+  const uint32_t nsegs = e->nsegs;
+  if (!nsegs) return refuse_all();  // (nothing to view, and no list to number: launch_yata)
   ViewBufs vb;
+  uint32_t narr = 0;
+  if (const int rc2 = view_workspace(e, nsegs, vb, narr)) return rc2;
+  const uint32_t nlists = e->nlists;
   const size_t ck = std::max<uint32_t>(w.cap_keys, 1);
-  vb.kmap = take<uint32_t>(V, B_VKMAP, ck, ok);
-  vb.krep = take<uint32_t>(V, B_VKREP, ck, ok);
-  vb.keys = take<ViewKey>(V, B_VKEYS, ck, ok);
-  vb.nkeys = take<uint32_t>(V, B_VNKEYS, 4, ok);
-  vb.pos_of = take<uint32_t>(V, B_VPOS, (size_t)nsegs + 1, ok);
-  vb.d0 = take<uint32_t>(V, B_VD0, (size_t)narr + 1, ok);
-  vb.n0 = take<uint32_t>(V, B_VN0, (size_t)narr + 1, ok);
-  vb.d1 = take<uint32_t>(V, B_VD1, (size_t)narr + 1, ok);
-  vb.n1 = take<uint32_t>(V, B_VN1, (size_t)narr + 1, ok);
-  vb.order = take<uint32_t>(V, B_VORDER, (size_t)narr + 1, ok);
-  vb.segs = take<ViewSeg>(V, B_VSEGS, (size_t)narr + 1, ok);
-  if (!ok) return fail(YCRDT_E_DEVICE, oom("view"));
   if ((uint64_t)ck + narr >= 0x7FFFFFF0ull) return refuse_all();
   // the requests, sorted by (document, root name hash), and their names
   const uint32_t nreq = (uint32_t)ws.size();
@@ -3281,8 +3222,8 @@ static uint64_t json_pass_bytes() {
 int ycrdt_docs_json(ycrdt_engine* e, ycrdt_doc* const* docs, const char* const* roots, const int* kinds, size_t n,
                     ycrdt_out* blob, uint64_t* offs, ycrdt_json_stats* st) {
   if (!e || !docs || !blob || !offs || (n && (!roots || !kinds))) return fail(YCRDT_E_ARG, "null arg");
+  if (const int rc = check_docs(e, docs, n)) return rc;
   for (size_t i = 0; i < n; ++i) {
-    if (!docs[i] || docs[i]->e != e) return fail(YCRDT_E_ARG, "document of another engine (or null) at " + std::to_string(i));
     if (!roots[i]) return fail(YCRDT_E_ARG, "null root at " + std::to_string(i));
     if (kinds[i] < 0 || kinds[i] > 1) return fail(YCRDT_E_ARG, "kind outside {0, 1} at " + std::to_string(i));
   }
@@ -3300,13 +3241,7 @@ int ycrdt_docs_json(ycrdt_engine* e, ycrdt_doc* const* docs, const char* const* 
   }
   if (n >= 0x7FFFFFFFull) return fail(YCRDT_E_CAPACITY, "too many requests");
   HIPCHK(hipSetDevice(e->device));
-  {
-    std::vector<ycrdt_doc*> q;
-    for (size_t i = 0; i < n; ++i) if (!docs[i]->queue.empty()) q.push_back(docs[i]);
-    std::sort(q.begin(), q.end());
-    q.erase(std::unique(q.begin(), q.end()), q.end());
-    if (const int rc = flush_multi(e, q)) return rc;
-  }
+  if (const int rc = flush_queued(e, docs, n)) return rc;
   // which path every request takes; the device path's distinct documents and triples
   enum : uint8_t { K_SINGLE = 0, K_EMPTY, K_DEV };
   const bool off = env_off("YCRDT_DOCS_JSON");
@@ -3434,13 +3369,7 @@ int ycrdt_encode_state_as_update(ycrdt_doc* d, ycrdt_buf sv, ycrdt_out* out) {
     main.resize(e->out_bytes);
     HIPCHK(hipMemcpy(main.data(), e->w.out, e->out_bytes, hipMemcpyDeviceToHost));
   }
-  if (!d->ing.has_pending && !d->ing.has_ds) {
-    out->len = main.size();
-    out->ptr = (uint8_t*)malloc(out->len);
-    if (!out->ptr) return fail(YCRDT_E_CAPACITY, "host allocation failed");
-    memcpy(out->ptr, main.data(), out->len);
-    return YCRDT_OK;
-  }
+  if (!d->ing.has_pending && !d->ing.has_ds) return out_set(out, main.data(), main.size());
   // encodeStateAsUpdateV2 (Y@22155): mergeUpdates([main, pendingDs, diffUpdate(pending, sv)])
   std::vector<ycrdt_buf> parts{ycrdt_buf{main.data(), main.size()}};
   if (d->ing.has_ds) parts.push_back(ycrdt_buf{d->ing.pending_ds.data(), d->ing.pending_ds.size()});
@@ -3463,12 +3392,7 @@ int ycrdt_encode_state_vector(ycrdt_doc* d, ycrdt_out* out) {
   out->len = 0;
   const int rc = flush(d);
   if (rc) return rc;
-  const std::vector<uint8_t>* src = &d->sv;  // device-written: descending, or store order (compat 135)
-  out->len = src->size();
-  out->ptr = (uint8_t*)malloc(out->len ? out->len : 1);
-  if (!out->ptr) { out->len = 0; return fail(YCRDT_E_CAPACITY, "host allocation failed"); }
-  if (out->len) memcpy(out->ptr, src->data(), out->len);
-  return YCRDT_OK;
+  return out_set(out, d->sv.data(), d->sv.size());  // device-written: descending, or store order (compat 135)
 }
 
 int ycrdt_doc_last_stats(ycrdt_doc* d, ycrdt_merge_stats* st) {
@@ -3615,18 +3539,11 @@ int ycrdt_comm_fleet_sv_allreduce_max(ycrdt_comm* c, ycrdt_engine* e, const uint
   std::vector<uint8_t> b;
   const int r = yc::comm_fleet_sv_allreduce_max(c, docs, svs, n, e->stream, d, o, b, err);
   if (r) return fail(r == -2 ? YCRDT_E_DECODE : r == -3 ? YCRDT_E_ARG : YCRDT_E_DEVICE, err);
-  auto give = [](ycrdt_out* x, const void* p, size_t len) -> bool {
-    x->ptr = (uint8_t*)malloc(len ? len : 1);
-    if (!x->ptr) return false;
-    x->len = len;
-    if (len) memcpy(x->ptr, p, len);
-    return true;
-  };
-  if (!give(doc_ids, d.data(), 4 * d.size()) || !give(offs, o.data(), 8 * o.size()) || !give(blob, b.data(), b.size())) {
+  if (out_set(doc_ids, d.data(), 4 * d.size()) || out_set(offs, o.data(), 8 * o.size()) || out_set(blob, b.data(), b.size())) {
     ycrdt_free(doc_ids);
     ycrdt_free(offs);
     ycrdt_free(blob);
-    return fail(YCRDT_E_CAPACITY, "host allocation failed");
+    return YCRDT_E_CAPACITY;  // (out_set's message stands)
   }
   return YCRDT_OK;
 }
@@ -3671,11 +3588,7 @@ int ycrdt_comm_sv_allreduce_max(ycrdt_comm* c, ycrdt_engine* e, ycrdt_buf sv, yc
   std::vector<uint8_t> o;
   const int r = yc::comm_sv_allreduce_max(c, sv.ptr, sv.len, e->stream, o, err);
   if (r) return fail(r == -2 ? YCRDT_E_DECODE : YCRDT_E_DEVICE, err);
-  out->len = o.size();
-  out->ptr = (uint8_t*)malloc(o.size() ? o.size() : 1);
-  if (!out->ptr) { out->len = 0; return fail(YCRDT_E_CAPACITY, "host allocation failed"); }
-  memcpy(out->ptr, o.data(), o.size());
-  return YCRDT_OK;
+  return out_set(out, o.data(), o.size());
 }
 
 int ycrdt_comm_allgather(ycrdt_comm* c, ycrdt_engine* e, ycrdt_buf mine, ycrdt_out* blob, ycrdt_out* offs) {
@@ -3757,10 +3670,7 @@ int ycrdt_merge_updates(ycrdt_engine* e, const ycrdt_buf* ups, size_t n, ycrdt_o
   out->ptr = nullptr;
   out->len = 0;
   if (n == 1) {  // mergeUpdatesV2 returns its single input unchanged (Y@39011)
-    out->len = ups[0].len;
-    out->ptr = (uint8_t*)malloc(out->len ? out->len : 1);
-    if (out->len) memcpy(out->ptr, ups[0].ptr, out->len);
-    return YCRDT_OK;
+    return out_set(out, ups[0].ptr, ups[0].len);
   }
   HIPCHK(hipSetDevice(e->device));
   ycrdt_batch& b = scratch_batch(e);  // engine-owned: no hipMalloc / hipFree per call
@@ -3773,10 +3683,8 @@ int ycrdt_diff_update(ycrdt_engine* e, ycrdt_buf update, ycrdt_buf sv, ycrdt_out
   if (!e || !out) return fail(YCRDT_E_ARG, "null arg");
   out->ptr = nullptr;
   out->len = 0;
-  std::unordered_map<uint32_t, uint32_t> m;
-  if (!parse_sv(sv.ptr, sv.len, m)) return fail(YCRDT_E_DECODE, "Integer out of range! (state vector)");
-  std::vector<std::pair<uint32_t, uint32_t>> v(m.begin(), m.end());
-  std::sort(v.begin(), v.end());
+  std::vector<std::pair<uint32_t, uint32_t>> v;
+  if (!parse_sv_sorted(sv.ptr, sv.len, v)) return fail(YCRDT_E_DECODE, "Integer out of range! (state vector)");
   HIPCHK(hipSetDevice(e->device));
   ycrdt_batch& b = scratch_batch(e);  // engine-owned: no hipMalloc / hipFree per call
   int rc = stage(&b, &update, 1, nullptr, 0);
@@ -3788,14 +3696,11 @@ int ycrdt_diff_updates(ycrdt_engine* e, const ycrdt_buf* updates, const ycrdt_bu
   if (!e || (n && (!updates || !svs || !outs))) return fail(YCRDT_E_ARG, "null arg");
   for (size_t i = 0; i < n; ++i) { outs[i].ptr = nullptr; outs[i].len = 0; }
   if (!n) return YCRDT_OK;
-  std::vector<std::pair<uint32_t, uint32_t>> v;
+  std::vector<std::pair<uint32_t, uint32_t>> v, one;
   std::vector<uint32_t> off(n + 1, 0);
   for (size_t i = 0; i < n; ++i) {
-    std::unordered_map<uint32_t, uint32_t> m;
-    if (!parse_sv(svs[i].ptr, svs[i].len, m)) return fail(YCRDT_E_DECODE, "Integer out of range! (state vector)");
-    const size_t v0 = v.size();
-    v.insert(v.end(), m.begin(), m.end());
-    std::sort(v.begin() + v0, v.end());
+    if (!parse_sv_sorted(svs[i].ptr, svs[i].len, one)) return fail(YCRDT_E_DECODE, "Integer out of range! (state vector)");
+    v.insert(v.end(), one.begin(), one.end());
     off[i + 1] = (uint32_t)v.size();
   }
   HIPCHK(hipSetDevice(e->device));
@@ -3881,13 +3786,11 @@ int ycrdt_doc_take_local_update(ycrdt_doc* d, ycrdt_out* out) {
   out->len = 0;
   d->track_local = true;  // from now on local ops are recorded for the next take
   const std::vector<std::vector<uint8_t>>& ops = d->local;
-  if (ops.empty()) return empty_update(out);
+  static const uint8_t empty_update[2] = {0, 0};
+  if (ops.empty()) return out_set(out, empty_update, 2);
   int rc = YCRDT_OK;
   if (ops.size() == 1) {  // Y.mergeUpdates returns a single input unchanged
-    out->ptr = (uint8_t*)malloc(ops[0].size() ? ops[0].size() : 1);
-    if (!out->ptr) return fail(YCRDT_E_CAPACITY, "host allocation failed");
-    out->len = ops[0].size();
-    memcpy(out->ptr, ops[0].data(), out->len);
+    rc = out_set(out, ops[0].data(), ops[0].size());
   } else {
     std::vector<ycrdt_buf> bufs;
     for (const auto& u : ops) bufs.push_back(ycrdt_buf{u.data(), u.size()});
@@ -3905,6 +3808,13 @@ static OpTarget target_of(const char* root, const char* parent_key) {
   return t;
 }
 
+// a JSON text with a NUL behind it (which the length leaves out)
+static int out_text(ycrdt_out* out, const std::string& j) {
+  const int rc = out_set(out, j.c_str(), j.size() + 1);
+  if (rc == YCRDT_OK) out->len = j.size();
+  return rc;
+}
+
 int ycrdt_type_json(ycrdt_doc* d, const char* root, const char* parent_key, int kind, ycrdt_out* out) {
   if (!d || !root || !out || kind < 0 || kind > 1) return fail(YCRDT_E_ARG, "bad arg");
   out->ptr = nullptr;
@@ -3913,14 +3823,8 @@ int ycrdt_type_json(ycrdt_doc* d, const char* root, const char* parent_key, int 
   if (rc) return rc;
   std::string j, err;
   if (!view_type_json(d->view, target_of(root, parent_key), kind, j, err)) return fail(YCRDT_E_DECODE, err);
-  out->len = j.size();
-  out->ptr = (uint8_t*)malloc(j.size() + 1);
-  if (!out->ptr) { out->len = 0; return fail(YCRDT_E_CAPACITY, "host allocation failed"); }
-  memcpy(out->ptr, j.data(), j.size());
-  out->ptr[j.size()] = 0;
-  return YCRDT_OK;
+  return out_text(out, j);
 }
-static int read_out(const std::string& j, ycrdt_out* out);
 int ycrdt_map_entries(ycrdt_doc* d, const char* root, const char* parent_key, ycrdt_out* out) {
   if (!d || !root || !out) return fail(YCRDT_E_ARG, "null arg");
   out->ptr = nullptr;
@@ -3929,7 +3833,7 @@ int ycrdt_map_entries(ycrdt_doc* d, const char* root, const char* parent_key, yc
   if (rc) return rc;
   std::string j;
   view_map_entries(d->view, target_of(root, parent_key), j);
-  return read_out(j, out);
+  return out_set(out, j.data(), j.size());
 }
 int ycrdt_doc_json(ycrdt_doc* d, const char* root, int kind, ycrdt_out* out) {
   if (!d || !root || !out || kind < 0 || kind > 1) return fail(YCRDT_E_ARG, "bad arg");
@@ -3939,11 +3843,7 @@ int ycrdt_doc_json(ycrdt_doc* d, const char* root, int kind, ycrdt_out* out) {
   if (rc) return rc;
   std::string j, err;
   if (!view_root_json(d->view, root, kind, j, err)) return fail(YCRDT_E_DECODE, err);
-  out->len = j.size();
-  out->ptr = (uint8_t*)malloc(j.size() + 1);
-  memcpy(out->ptr, j.data(), j.size());
-  out->ptr[j.size()] = 0;
-  return YCRDT_OK;
+  return out_text(out, j);
 }
 
 int ycrdt_map_type_at(ycrdt_doc* d, const char* root, const char* key, int32_t* type_ref) {
@@ -3954,33 +3854,31 @@ int ycrdt_map_type_at(ycrdt_doc* d, const char* root, const char* key, int32_t* 
   return YCRDT_OK;
 }
 
-int ycrdt_map_set(ycrdt_doc* d, const char* root, const char* parent_key, const char* key, const uint8_t* any,
-                  size_t anylen) {
-  if (!d || !root || !key || (!any && anylen)) return fail(YCRDT_E_ARG, "null arg");
-  if (!any_values_ok(any, anylen, 1)) return fail(YCRDT_E_ARG, "bad any value");
+// YMap.set of an item with content reference `ref` (8 ContentAny, 7 ContentType)
+static int map_set_content(ycrdt_doc* d, const char* root, const char* parent_key, const char* key, uint8_t ref,
+                           const std::vector<uint8_t>& content) {
   int rc = ensure_view(d);
   if (rc) return rc;
-  std::vector<uint8_t> content{1};  // ContentAny([value])
-  content.insert(content.end(), any, any + anylen);
   std::vector<uint8_t> u;
   std::string err;
-  rc = encode_map_set(d->view, target_of(root, parent_key), key, d->client_id, next_clock(d), 8, content.data(),
+  rc = encode_map_set(d->view, target_of(root, parent_key), key, d->client_id, next_clock(d), ref, content.data(),
                       content.size(), u, err);
   if (rc) return fail(rc, err);
   return apply_local(d, u);
 }
 
+int ycrdt_map_set(ycrdt_doc* d, const char* root, const char* parent_key, const char* key, const uint8_t* any,
+                  size_t anylen) {
+  if (!d || !root || !key || (!any && anylen)) return fail(YCRDT_E_ARG, "null arg");
+  if (!any_values_ok(any, anylen, 1)) return fail(YCRDT_E_ARG, "bad any value");
+  std::vector<uint8_t> content{1};  // ContentAny([value])
+  content.insert(content.end(), any, any + anylen);
+  return map_set_content(d, root, parent_key, key, 8, content);
+}
+
 int ycrdt_map_set_type(ycrdt_doc* d, const char* root, const char* parent_key, const char* key, uint32_t type_ref) {
   if (!d || !root || !key || type_ref > 1) return fail(YCRDT_E_ARG, "bad arg (type_ref: 0 = YArray, 1 = YMap)");
-  int rc = ensure_view(d);
-  if (rc) return rc;
-  std::vector<uint8_t> content{(uint8_t)type_ref};  // ContentType: writeTypeRef
-  std::vector<uint8_t> u;
-  std::string err;
-  rc = encode_map_set(d->view, target_of(root, parent_key), key, d->client_id, next_clock(d), 7, content.data(),
-                      content.size(), u, err);
-  if (rc) return fail(rc, err);
-  return apply_local(d, u);
+  return map_set_content(d, root, parent_key, key, 7, {(uint8_t)type_ref});  // ContentType: writeTypeRef
 }
 
 int ycrdt_map_delete(ycrdt_doc* d, const char* root, const char* parent_key, const char* key) {
@@ -4029,14 +3927,6 @@ int ycrdt_array_delete(ycrdt_doc* d, const char* root, const char* parent_key, u
 
 // Per-key reads (YMap.get / has / size, YArray.length / get): the view's hash index, no JSON of
 // the whole type. The first read after a change merges the queue and rebuilds the view, as toJSON.
-static int read_out(const std::string& j, ycrdt_out* out) {
-  out->len = j.size();
-  out->ptr = (uint8_t*)malloc(j.size() + 1);
-  if (!out->ptr) { out->len = 0; return fail(YCRDT_E_CAPACITY, "host allocation failed"); }
-  memcpy(out->ptr, j.data(), j.size());
-  return YCRDT_OK;
-}
-
 int ycrdt_map_get(ycrdt_doc* d, const char* root, const char* parent_key, const char* key, int* state, ycrdt_out* json) {
   if (!d || !root || !key || !state || !json) return fail(YCRDT_E_ARG, "null arg");
   json->ptr = nullptr;
@@ -4045,7 +3935,7 @@ int ycrdt_map_get(ycrdt_doc* d, const char* root, const char* parent_key, const 
   if (rc) return rc;
   std::string j;
   view_map_get(d->view, target_of(root, parent_key), key, *state, j);
-  return read_out(j, json);
+  return out_set(json, j.data(), j.size());
 }
 
 int ycrdt_map_size(ycrdt_doc* d, const char* root, const char* parent_key, uint32_t* size) {
@@ -4072,7 +3962,7 @@ int ycrdt_array_get(ycrdt_doc* d, const char* root, const char* parent_key, uint
   if (rc) return rc;
   std::string j;
   view_array_get(d->view, target_of(root, parent_key), index, *state, j);
-  return read_out(j, json);
+  return out_set(json, j.data(), j.size());
 }
 
 int ycrdt_validate_update(ycrdt_buf update, int* structs_ok) {
@@ -4083,13 +3973,8 @@ int ycrdt_validate_update(ycrdt_buf update, int* structs_ok) {
   return ok ? YCRDT_OK : fail(YCRDT_E_DECODE, "Integer out of range!");
 }
 
-static int out_copy(ycrdt_out* o, const std::vector<uint8_t>& v) {
-  if (!o) return YCRDT_OK;
-  o->ptr = (uint8_t*)malloc(v.size() ? v.size() : 1);
-  if (!o->ptr) { o->len = 0; return fail(YCRDT_E_CAPACITY, "host allocation failed"); }
-  o->len = v.size();
-  if (!v.empty()) memcpy(o->ptr, v.data(), v.size());
-  return YCRDT_OK;
+static int out_copy(ycrdt_out* o, const std::vector<uint8_t>& v) {  // (an output the caller did not ask for: skipped)
+  return o ? out_set(o, v.data(), v.size()) : (int)YCRDT_OK;
 }
 
 int ycrdt_debug_replay(const ycrdt_buf* ups, size_t n, ycrdt_merge_fn merge, void* ctx, ycrdt_out* sv, ycrdt_out* pending,

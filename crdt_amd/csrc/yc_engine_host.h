@@ -1,0 +1,84 @@
+// yc_engine_host.h — the engine host layer's helpers that make no HIP call: state-vector parsing, the
+// byte layout of a doc's marks block. The header builds with a plain C++ compiler (tests/csrc/engine_host_main.cpp runs it under the sanitizers).
+#pragma once
+#include <algorithm>
+#include <cstddef>
+#include <cstdint>
+#include <cstdlib>
+#include <cstring>
+#include <unordered_map>
+#include <utility>
+#include <vector>
+
+#pragma GCC visibility push(hidden)
+namespace yc {
+
+// decode a state vector (varuint n, (client, clock) × n): put(client, clock) per entry
+template <class Put>
+bool parse_sv_each(const uint8_t* p, size_t n, Put put) {
+  size_t pos = 0;
+  auto vu = [&](uint32_t& v) -> bool {
+    uint32_t r = 0;
+    int shift = 0;
+    for (;;) {
+      if (pos >= n) return false;
+      uint32_t b = p[pos++];
+      if (shift < 32) r |= (b & 0x7fu) << shift;
+      shift += 7;
+      if (b < 0x80) { v = r; return true; }
+      if (shift >= 35) return false;  // (a 32-bit value ends within 5 bytes: a 6th is refused, not dropped)
+    }
+  };
+  uint32_t k;
+  if (!vu(k)) return false;
+  for (uint32_t i = 0; i < k; ++i) {
+    uint32_t c, cl;
+    if (!vu(c) || !vu(cl)) return false;
+    put(c, cl);
+  }
+  return true;
+}
+inline bool parse_sv(const uint8_t* p, size_t n, std::unordered_map<uint32_t, uint32_t>& out) {
+  return parse_sv_each(p, n, [&](uint32_t c, uint32_t cl) { out[c] = cl; });
+}
+// the same as (client, clock) pairs with the clients ascending (a client named twice: its last
+// clock, as the map gives). Yjs writes state vectors in descending or store order: no hashing,
+// and no sort when the input is already in either order.
+inline bool parse_sv_sorted(const uint8_t* p, size_t n, std::vector<std::pair<uint32_t, uint32_t>>& v) {
+  v.clear();
+  if (!parse_sv_each(p, n, [&](uint32_t c, uint32_t cl) { v.emplace_back(c, cl); })) return false;
+  auto before = [](const std::pair<uint32_t, uint32_t>& a, const std::pair<uint32_t, uint32_t>& b) { return a.first < b.first; };
+  auto after = [](const std::pair<uint32_t, uint32_t>& a, const std::pair<uint32_t, uint32_t>& b) { return a.first > b.first; };
+  if (std::adjacent_find(v.begin(), v.end(), [&](const auto& a, const auto& b) { return !before(a, b); }) == v.end()) return true;
+  if (std::adjacent_find(v.begin(), v.end(), [&](const auto& a, const auto& b) { return !after(a, b); }) == v.end()) {
+    std::reverse(v.begin(), v.end());
+    return true;
+  }
+  std::stable_sort(v.begin(), v.end(), before);
+  size_t w = 0;
+  for (size_t i = 0; i < v.size(); ++i) {
+    if (i + 1 < v.size() && v[i + 1].first == v[i].first) continue;  // (the last of equal clients wins)
+    v[w++] = v[i];
+  }
+  v.resize(w);
+  return true;
+}
+
+// The marks block of a doc (yc_work.h PreMarks; written by k_state_marks, read by k_predecoded and the
+// sync replies): fbits[nw] | sbits[nw] | secs[cap] | meta, nw = the state's 64-byte words, cap = its
+// client slots + 1, section_bytes = sizeof(Section). THE definition of the block's byte layout: the
+// allocation and every reader take their offsets from here (fbits is at 0).
+struct MarksLayout {
+  size_t sbits, secs, meta, bytes;
+};
+inline MarksLayout marks_layout(uint32_t nw, uint32_t cap, size_t section_bytes) {
+  MarksLayout m;
+  m.sbits = 8ull * nw;
+  m.secs = 16ull * nw;
+  m.meta = m.secs + section_bytes * cap;
+  m.bytes = m.meta + 16;
+  return m;
+}
+
+}  // namespace yc
+#pragma GCC visibility pop
