@@ -579,15 +579,16 @@ __device__ __attribute__((noinline)) uint32_t any_canon(const uint8_t* __restric
     for (int s = 56; s >= 0; s -= 8) put((uint32_t)(c.u >> s) & 0xFFu);
   };
   bool ok = true;
-  // members left per open container level (the elements of the content are one implicit level)
-  uint32_t rem[33];
-  uint32_t objm = 0;  // bit d: level d is an object
+  // Members left per kept container level. As in skip_any (yc_parse.h), whose 32 levels admitted the
+  // content: a level is kept only while members follow the one being read; a container's last member
+  // is read in the container's place, so nesting along last members, however deep, takes no level.
+  // (The output needs no closers: a container is its tag, its count and its members in order.)
+  uint32_t rem[32];
+  uint32_t objm = 0;  // bit d: kept level d is an object
   int d = 0;
-  rem[0] = e1;
-  uint32_t idx = 0;  // content element index at level 0
-  for (;;) {
+  uint32_t idx = 0;  // content element index
+  while (idx < e1) {
     // one value at p
-    if (d == 0 && idx >= e1) break;
     const bool emit = idx >= e0;  // (constant while inside one content element)
     const uint32_t tag = by[p++];
     const uint32_t s0 = p;
@@ -613,27 +614,28 @@ __device__ __attribute__((noinline)) uint32_t any_canon(const uint8_t* __restric
         const uint32_t n = rd_vu(by, p, end, ok);
         if (emit) { put(tag); put_vu(n); }
         if (n > 0) {
-          if (d >= 32) return 0;  // (the decoder's stack bound: never reached for flagged content)
-          ++d;
-          rem[d] = n;
-          if (tag == 118) objm |= 1u << d; else objm &= ~(1u << d);
+          if (n > 1) {  // members follow the first: keep the level
+            if (d == 32) return 0;  // (the decoder's stack bound: never reached for content it admitted)
+            rem[d] = n - 1;
+            if (tag == 118) objm |= 1u << d; else objm &= ~(1u << d);
+            ++d;
+          }
           if (tag == 118) { const uint32_t k = rd_vu(by, p, end, ok); if (emit) { put_vu(k); for (uint32_t i = 0; i < k; ++i) put(by[p + i]); } p += k; }
-          continue;
+          continue;  // the first member's value
         }
         break;
       }
     }
-    // a value completed: pop finished levels, read the next key of an object
-    for (;;) {
-      if (d == 0) { ++idx; break; }
-      if (--rem[d] == 0) { --d; continue; }
-      if ((objm >> d) & 1u) {
-        const uint32_t k = rd_vu(by, p, end, ok);
-        if (idx >= e0) { put_vu(k); for (uint32_t i = 0; i < k; ++i) put(by[p + i]); }
-        p += k;
-      }
-      break;
+    // a value completed: with no level kept the content element is complete; else the innermost kept
+    // level moves to its next member (the key of an object first), its last one read in its place
+    if (d == 0) { ++idx; continue; }
+    const uint32_t lvl = (uint32_t)d - 1;
+    if ((objm >> lvl) & 1u) {
+      const uint32_t k = rd_vu(by, p, end, ok);
+      if (emit) { put_vu(k); for (uint32_t i = 0; i < k; ++i) put(by[p + i]); }
+      p += k;
     }
+    if (--rem[lvl] == 0) --d;
   }
   return (uint32_t)(q - q0);
 }

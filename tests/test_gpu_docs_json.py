@@ -4,6 +4,12 @@ JSON text sized, laid out and written on the device (yc_json.hip). Every answer 
 to the per-document Doc.root_json — the host writer over the same view — and, where the fixtures
 record it, equal to Yjs 13.5.16's own toJSON().
 
+The equality with Doc.root_json is a consistency check, not a reference: both writers are built
+from the same yc_json.h, so a wrong digit, escape or comma there passes on both sides, and the
+json.loads comparisons are blind to the text form. What holds the text itself — Node's bytes, an
+exact number reference and the host build under sanitizers — is tests/test_gpu_json_values.py
+with tests/test_num_text.py and tests/test_jsnum_reference.py.
+
 Hand-written updates (Yjs v1 wire format, one client each) build the shapes the fixtures lack: entry
 names that stress the ordering, lists that cross the 256-lane blocks of the scans, types nested to
 the device path's depth bound and one level past it.
