@@ -12,6 +12,9 @@ the C ABI in include/ycrdt.h (libycrdt.so, hand-written gfx950 HIP kernels):
     merge_updates([u8])           Y.mergeUpdates                   north_star (Y@39011)
     diff_update(u8, sv)           Y.diffUpdate                     Y@40711
     diff_updates(u8s, svs)        n x Y.diffUpdate, one batched pass (crdt.js:286-291 sync responder)
+    merge_update_groups(groups)   Y.mergeUpdates per group, one batched pass (crdt.js:79-98 logs, compacted)
+    state_vector_from_update(u8)  Y.encodeStateVectorFromUpdate    crdt.js:28-77 without the temporary docs
+    state_vectors_from_updates(u8s)  the same for n updates, one batched pass
 
 Errors raise YcrdtError (the reference only reads `e.message`, crdt.js:38-39). There is no CPU
 fallback: importing works without a GPU, but every compute call needs the HIP device.
@@ -22,6 +25,8 @@ import os
 __all__ = [
     "YcrdtError", "Engine", "Doc", "Batch", "MergeStats", "apply_update", "apply_updates",
     "encode_state_as_update", "encode_state_vector", "merge_updates", "diff_update", "diff_updates", "default_engine", "library_path",
+    "StoreStats", "merge_update_groups", "merge_update_groups_stats", "state_vectors_from_updates", "state_vectors_from_updates_stats",
+    "state_vector_from_update",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -100,6 +105,19 @@ class JsonStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class StoreStats(ctypes.Structure):
+    _fields_ = [
+        ("groups_device", ctypes.c_uint64),
+        ("groups_single", ctypes.c_uint64),
+        ("groups_copied", ctypes.c_uint64),
+        ("out_bytes", ctypes.c_uint64),
+        ("device_ms", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 def library_path():
     # YCRDT_LIB: another build of the library (A/B experiments); the in-tree one by default
     return os.environ.get("YCRDT_LIB") or os.path.join(_HERE, "libycrdt.so")
@@ -121,6 +139,7 @@ EXPORTS = (
     "ycrdt_comm_sv_allreduce_max", "ycrdt_comm_ds_allgather", "ycrdt_comm_create_exchange", "ycrdt_route",
     "ycrdt_comm_fleet_sv_allreduce_max", "ycrdt_docs_states_packed", "ycrdt_comm_allgather", "ycrdt_device_count",
     "ycrdt_docs_diff", "ycrdt_docs_json",
+    "ycrdt_merge_updates_groups", "ycrdt_updates_state_vectors", "ycrdt_update_state_vector",
 )
 
 MERGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p)
@@ -201,6 +220,9 @@ def lib():
     L.ycrdt_route.argtypes = [ctypes.c_char_p, sz, u32]
     L.ycrdt_docs_diff.argtypes = [vp, P(vp), P(_Buf), sz, P(_Out), P(ctypes.c_uint64), P(SyncStats)]
     L.ycrdt_docs_json.argtypes = [vp, P(vp), P(cs), P(i32), sz, P(_Out), P(ctypes.c_uint64), P(JsonStats)]
+    L.ycrdt_merge_updates_groups.argtypes = [vp, P(_Buf), P(u32), sz, u32, P(_Out), P(ctypes.c_uint64), P(StoreStats)]
+    L.ycrdt_updates_state_vectors.argtypes = [vp, P(_Buf), sz, P(_Out), P(ctypes.c_uint64), P(StoreStats)]
+    L.ycrdt_update_state_vector.argtypes = [vp, _Buf, P(_Out)]
     L.ycrdt_route.restype = u32
     L.ycrdt_comm_fleet_sv_allreduce_max.argtypes = [vp, vp, P(u32), P(_Buf), sz, P(_Out), P(_Out), P(_Out)]
     L.ycrdt_map_size.argtypes = [vp, cs, cs, P(u32)]
@@ -834,3 +856,81 @@ def docs_json(docs, roots, kinds, engine=None) -> list:
 def docs_diff(docs, svs, engine=None) -> list:
     """[Y.encodeStateAsUpdate(d, sv) for d, sv in zip(docs, svs)] in one device pass (docs_diff_stats)."""
     return docs_diff_stats(docs, svs, engine)[0]
+
+
+def merge_update_groups_stats(groups, engine=None, group_of=None, ngroups=None):
+    """([Y.mergeUpdates(g) for g in groups], stats) in one device pass (ycrdt_merge_updates_groups):
+    compacting the logs of many topics at once (crdt.js:79-98 replays a log that is never compacted).
+    groups: a list of update lists. With group_of (one group index per update) and ngroups, `groups`
+    is instead the flat update list in arrival order — groups may interleave, each keeps its order.
+    stats: ycrdt_store_stats as a dict (which path the groups took)."""
+    import numpy as np
+
+    eng = engine or default_engine()
+    if group_of is None:
+        flat = [bytes(u) for g in groups for u in g]
+        gof = np.fromiter((i for i, g in enumerate(groups) for _ in g), dtype=np.uint32, count=len(flat))
+        ng = len(groups)
+    else:
+        flat = [bytes(u) for u in groups]
+        gof = np.asarray(group_of, dtype=np.uint32)
+        ng = int(ngroups)
+        if len(gof) != len(flat):
+            raise ValueError("merge_update_groups: one group index per update")
+    arr, keep = _bufs(flat)
+    gof = np.ascontiguousarray(gof if len(gof) else np.zeros(1, np.uint32))
+    offs = np.zeros(ng + 1, dtype=np.uint64)
+    out = _Out()
+    st = StoreStats()
+    _check(lib().ycrdt_merge_updates_groups(eng._h, arr, gof.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), len(keep), ng,
+                                            ctypes.byref(out), offs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ctypes.byref(st)))
+    try:
+        o = offs.tolist()
+        if out.len < 4096 * ng:  # small results: one copy of the blob, sliced (a ctypes call each costs more)
+            blob = ctypes.string_at(out.ptr, out.len) if out.len else b""
+            return [blob[o[i]:o[i + 1]] for i in range(ng)], st.as_dict()
+        return [ctypes.string_at(out.ptr + o[i], o[i + 1] - o[i]) for i in range(ng)], st.as_dict()
+    finally:
+        lib().ycrdt_free(ctypes.byref(out))
+
+
+def merge_update_groups(groups, engine=None) -> list:
+    """[Y.mergeUpdates(g) for g in groups] in one device pass (merge_update_groups_stats)."""
+    return merge_update_groups_stats(groups, engine)[0]
+
+
+def state_vectors_from_updates_stats(updates, engine=None):
+    """([Y.encodeStateVectorFromUpdate(u) for u in updates], stats) in one device pass
+    (ycrdt_updates_state_vectors): what a doc-less store holds of every topic, without the temporary
+    doc of crdt.js:28-77. stats: ycrdt_store_stats as a dict (groups_* count updates)."""
+    import numpy as np
+
+    eng = engine or default_engine()
+    arr, keep = _bufs([bytes(u) for u in updates])
+    n = len(keep)
+    offs = np.zeros(n + 1, dtype=np.uint64)
+    out = _Out()
+    st = StoreStats()
+    _check(lib().ycrdt_updates_state_vectors(eng._h, arr, n, ctypes.byref(out), offs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+                                             ctypes.byref(st)))
+    try:
+        o = offs.tolist()
+        blob = ctypes.string_at(out.ptr, out.len) if out.len else b""
+        return [blob[o[i]:o[i + 1]] for i in range(n)], st.as_dict()
+    finally:
+        lib().ycrdt_free(ctypes.byref(out))
+
+
+def state_vectors_from_updates(updates, engine=None) -> list:
+    """[Y.encodeStateVectorFromUpdate(u) for u in updates] in one device pass (state_vectors_from_updates_stats)."""
+    return state_vectors_from_updates_stats(updates, engine)[0]
+
+
+def state_vector_from_update(update: bytes, engine=None) -> bytes:
+    """Y.encodeStateVectorFromUpdate(update) on the GPU (ycrdt_update_state_vector)."""
+    eng = engine or default_engine()
+    u = bytes(update)
+    bu = _Buf(ctypes.cast(ctypes.c_char_p(u), ctypes.c_void_p), len(u))
+    out = _Out()
+    _check(lib().ycrdt_update_state_vector(eng._h, bu, ctypes.byref(out)))
+    return _take(out)

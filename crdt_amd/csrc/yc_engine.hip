@@ -25,6 +25,7 @@
 #include "yc_comm.h"
 #include "yc_sync.h"
 #include "yc_json.h"
+#include "yc_store.h"
 #include <thread>
 #include <atomic>
 #include "../../include/ycrdt.h"
@@ -172,6 +173,7 @@ enum Buf {
   B_OFIRST, B_OCIDX, B_OSIZE, B_OPOS, B_RSEG, B_RLEN, B_RSIZE, B_RPOS, B_OUT, B_SVOUT,
   B_VKMAP, B_VKREP, B_VKEYS, B_VNKEYS, B_VPOS, B_VD0, B_VN0, B_VD1, B_VN1, B_VORDER, B_VSEGS,
   B_SCRATCH2, B_TMP2, B_CAPS, B_CLKEY, B_CLKEY2, B_CHKEY, B_CHVAL, B_CLDOC, B_DSFA, B_EMIT, B_DOCRNG, B_PACK, B_PACKPC, B_SPLITMETA, B_CLSINGLE, B_KSHARD, B_SOWNER, B_GFLAGS0, B_GFACC, B_LZBCLIENT, B_SYNC, B_SYNCPLAN, B_JSON, B_JSONUP,
+  B_STSKIP, B_STSIZE, B_STOFFS, B_STOUT, B_SG, B_SGOFFS, B_SGSIZE, B_SGSKIP, B_SGHPRE, B_DRGROUP,
   B_COUNT
 };
 
@@ -1830,32 +1832,13 @@ int split_multi(ycrdt_engine* e, const Decoded& D, uint32_t nr, uint32_t sbytes,
   return YCRDT_OK;
 }
 
-// With sv_off (diff only): update u is diffed against sv[sv_off[u] .. sv_off[u+1]) and `multi`
-// receives one encoded update per input update (the kernels write header-less block and
-// delete-set bytes; the per-update headers are written here while the bytes are split).
-int run_lazy(ycrdt_engine* e, ycrdt_batch* b, bool merge, const std::vector<std::pair<uint32_t, uint32_t>>& sv,
-             ycrdt_out* out, const std::vector<uint32_t>* sv_off = nullptr,
-             ycrdt_out* multi = nullptr) {
-  if (b->nwin > 1) return fail(YCRDT_E_CAPACITY, "mergeUpdates / diffUpdate of more than 4 GiB");
+// The workspace of the lazy merge / diff over a decoded batch (run_lazy, run_lazy_groups): NBLK
+// output blocks, SLOTS event slots; scan_extra: the longest scan of the caller's own.
+bool lazy_workspace(ycrdt_engine* e, const ycrdt_batch* b, const Decoded& D, bool seq, uint64_t NBLK, uint64_t SLOTS, uint64_t scan_extra) {
   Work& w = e->w;
-  w.lz_multi = 0;
-  w.capped = 0;
-  w.ds_first = e->compat == 135 ? 1u : 0u;
-  e->ws_owner = nullptr;
   auto& V = e->bufs;
-  g_bufs = &V;
   bool ok = true;
-  hipStream_t s = e->stream;
-  Decoded D;
-  int rc = run_decode(e, b, true, D);
-  if (rc) return rc;
-  Counters c;
-  const uint64_t NSEC = D.nsections + 2, NC = D.nclients + 2;
-  const bool seq = merge && D.noncanon;  // the serial mergeUpdates loop: output sections follow the events
-  const uint64_t NBLK0 = (merge ? D.nclients : D.nsections) + 2;
-  const uint64_t SLOTS = 2ull * D.nstructs + 2ull * NBLK0 + 4;
-  const uint64_t NBLK = seq ? SLOTS + 2 : NBLK0;
-  const uint64_t NDS = D.nds + 2;
+  const uint64_t NSEC = D.nsections + 2, NC = D.nclients + 2, NDS = D.nds + 2;
   w.lz_key = take<uint64_t>(V, B_LZKEY, NSEC, ok);
   w.lz_keys = take<uint64_t>(V, B_LZKEYS, NSEC, ok);
   w.lz_iota = take<uint32_t>(V, B_LZIOTA, NSEC, ok);
@@ -1896,11 +1879,41 @@ int run_lazy(ycrdt_engine* e, ycrdt_batch* b, bool merge, const std::vector<std:
   w.dw_pos = take<uint32_t>(V, B_DWPOS, NDS, ok);
   w.ds_fa = w.ds_first ? take<uint32_t>(V, B_DSFA, NDS, ok) : nullptr;
   {
-    size_t tb = prim_tmp_bytes(std::max<uint64_t>({((uint64_t)b->nbytes + 64) / 64 + 4, SLOTS, NDS, NSEC, 1024}),
+    size_t tb = prim_tmp_bytes(std::max<uint64_t>({((uint64_t)b->nbytes + 64) / 64 + 4, SLOTS, NDS, NSEC, scan_extra, 1024}),
                                std::max<uint64_t>(NSEC, NDS));
     w.tmp = take<uint8_t>(V, B_TMP, tb, ok);
     w.tmp_bytes = V[B_TMP].cap;
   }
+  return ok;
+}
+
+// With sv_off (diff only): update u is diffed against sv[sv_off[u] .. sv_off[u+1]) and `multi`
+// receives one encoded update per input update (the kernels write header-less block and
+// delete-set bytes; the per-update headers are written here while the bytes are split).
+int run_lazy(ycrdt_engine* e, ycrdt_batch* b, bool merge, const std::vector<std::pair<uint32_t, uint32_t>>& sv,
+             ycrdt_out* out, const std::vector<uint32_t>* sv_off = nullptr,
+             ycrdt_out* multi = nullptr) {
+  if (b->nwin > 1) return fail(YCRDT_E_CAPACITY, "mergeUpdates / diffUpdate of more than 4 GiB");
+  Work& w = e->w;
+  w.lz_multi = 0;
+  w.sg = nullptr;  // (not the groups mode of run_lazy_groups)
+  w.sg_skip = nullptr;
+  w.capped = 0;
+  w.ds_first = e->compat == 135 ? 1u : 0u;
+  e->ws_owner = nullptr;
+  auto& V = e->bufs;
+  g_bufs = &V;
+  bool ok = true;
+  hipStream_t s = e->stream;
+  Decoded D;
+  int rc = run_decode(e, b, true, D);
+  if (rc) return rc;
+  Counters c;
+  const bool seq = merge && D.noncanon;  // the serial mergeUpdates loop: output sections follow the events
+  const uint64_t NBLK0 = (merge ? D.nclients : D.nsections) + 2;
+  const uint64_t SLOTS = 2ull * D.nstructs + 2ull * NBLK0 + 4;
+  const uint64_t NBLK = seq ? SLOTS + 2 : NBLK0;
+  ok = lazy_workspace(e, b, D, seq, NBLK, SLOTS, 0);
   const size_t nsvo = sv_off ? sv_off->size() : 0;
   uint32_t* svbuf = take<uint32_t>(V, B_SVC, 2 * sv.size() + nsvo + 2, ok);
   if (!ok) return fail(YCRDT_E_DEVICE, oom("lazy merge workspace"));
@@ -2079,6 +2092,75 @@ int d2h_span(ycrdt_engine* e, uint8_t* host, const uint8_t* dev, uint64_t span) 
       for (auto& t : th) t.join();
     }
   }
+  return YCRDT_OK;
+}
+
+// mergeUpdates of every document (= group) of a staged multi-document batch in one pass
+// (ycrdt_merge_updates_groups; yc_lazy.hip "groups mode"): group g's update is dst[offs[g] ..
+// offs[g + 1]) (dst: malloc'ed, the caller's), skip[g] != 0 marks a group left out because it holds a
+// non-canonical update (no bytes: the caller merges it alone).
+int run_lazy_groups(ycrdt_engine* e, ycrdt_batch* b, uint8_t** dst, std::vector<uint64_t>& offs, std::vector<uint32_t>& skip, double* ms) {
+  *dst = nullptr;
+  if (b->nwin > 1) return fail(YCRDT_E_CAPACITY, "mergeUpdates of more than 4 GiB of groups");
+  Work& w = e->w;
+  w.lz_multi = 1;  // no batch-wide headers: every group has its own
+  w.sg = nullptr;
+  w.sg_skip = nullptr;
+  w.capped = 0;
+  w.ds_first = 0;
+  e->ws_owner = nullptr;
+  auto& V = e->bufs;
+  g_bufs = &V;
+  hipStream_t s = e->stream;
+  Decoded D;
+  int rc = run_decode(e, b, true, D);
+  if (rc) return rc;
+  const uint32_t nd = b->ndocs;
+  Counters c;
+  const uint64_t NBLK = D.nclients + 2, SLOTS = 2ull * D.nstructs + 2ull * NBLK + 4;
+  bool ok = lazy_workspace(e, b, D, false, NBLK, SLOTS, (uint64_t)nd + 2);
+  w.sg = take<LzGroup>(V, B_SG, (size_t)nd + 1, ok);
+  w.sg_offs = take<uint64_t>(V, B_SGOFFS, (size_t)nd + 2, ok);
+  w.sg_size = take<uint32_t>(V, B_SGSIZE, (size_t)nd + 2, ok);
+  w.sg_skip = take<uint32_t>(V, B_SGSKIP, (size_t)nd + 2, ok);
+  w.sg_hpre = take<uint32_t>(V, B_SGHPRE, NBLK, ok);
+  w.dr_group = take<uint32_t>(V, B_DRGROUP, (size_t)D.nds + 2, ok);
+  if (!ok) return fail(YCRDT_E_DEVICE, oom("lazy merge workspace (groups)"));
+  mark(e, "lazy.merge");
+  launch_groups_canon(w, s);
+  if (D.nsections) launch_lazy_merge(w, D.nsections, D.nclients, s);
+  else { w.lz_nblk = 0; w.lz_diff = 0; HIPCHK(hipMemsetAsync(w.lz_evbase, 0, sizeof(uint32_t) * 2, s)); }
+  rc = check(e, c, "mergeUpdates (groups)");
+  if (rc) return rc;
+  mark(e, "lazy.sizes");
+  uint32_t nslots = 0;
+  if (w.lz_nblk) launch_event_sizes(w, s, &nslots);
+  const uint32_t nr = launch_groups_ds_runs(w, D.nds, s);
+  launch_groups_layout(w, nr, s);
+  offs.assign((size_t)nd + 1, 0);
+  skip.assign(nd, 0);
+  HIPCHK(hipMemcpyAsync(offs.data(), w.sg_offs, sizeof(uint64_t) * ((size_t)nd + 1), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(skip.data(), w.sg_skip, sizeof(uint32_t) * nd, hipMemcpyDeviceToHost, s));
+  rc = check(e, c, "lazy sizes (groups)");
+  if (rc) return rc;
+  const uint64_t total = offs[nd];
+  if (total >= 0xFFFFFFF0ull) return fail(YCRDT_E_CAPACITY, "mergeUpdates of groups: more than 4 GiB of output");
+  w.out = take<uint8_t>(V, B_OUT, (size_t)total + 16, ok);
+  if (!ok) return fail(YCRDT_E_DEVICE, oom("output"));
+  mark(e, "lazy.write");
+  launch_groups_write(w, nslots, nr, s);
+  mark(e, "end");
+  HIPCHK(hipEventRecord(e->ev1, s));
+  uint8_t* o = (uint8_t*)malloc(total ? total : 1);
+  if (!o) return fail(YCRDT_E_CAPACITY, "host allocation failed");
+  rc = d2h_span(e, o, w.out, total);
+  if (rc == YCRDT_OK) rc = check(e, c, "lazy write (groups)");
+  if (rc) { free(o); return rc; }
+  collect_phase_ms(e);
+  float t = 0;
+  hipEventElapsedTime(&t, e->ev0, e->ev1);
+  *ms = t;
+  *dst = o;
   return YCRDT_OK;
 }
 
@@ -3708,6 +3790,192 @@ int ycrdt_diff_updates(ycrdt_engine* e, const ycrdt_buf* updates, const ycrdt_bu
   int rc = stage(&b, updates, n, nullptr, 0);
   if (rc == YCRDT_OK) rc = run_lazy(e, &b, false, v, nullptr, &off, outs);
   return rc;
+}
+
+// ---- the doc-less update store (yc_store.hip)
+
+// Y.encodeStateVectorFromUpdate of every update: the batch is staged and decoded in lazy mode as
+// one document (the client table is not read), the kernels size, lay out and write the state
+// vectors into one HBM buffer, and the offsets (one sync, with the counters) and the bytes come back.
+int ycrdt_updates_state_vectors(ycrdt_engine* e, const ycrdt_buf* ups, size_t n, ycrdt_out* blob, uint64_t* offs,
+                                ycrdt_store_stats* st) {
+  if (!e || !blob || !offs || (n && !ups)) return fail(YCRDT_E_ARG, "null arg");
+  blob->ptr = nullptr;
+  blob->len = 0;
+  offs[0] = 0;
+  ycrdt_store_stats S{};
+  if (st) *st = S;
+  for (size_t i = 0; i < n; ++i)
+    if (ups[i].len && !ups[i].ptr) return fail(YCRDT_E_ARG, "null update at " + std::to_string(i));
+  if (n == 0) {
+    blob->ptr = (uint8_t*)malloc(1);
+    if (!blob->ptr) return fail(YCRDT_E_CAPACITY, "host allocation failed");
+    return YCRDT_OK;
+  }
+  if (n >= 0x7FFFFFFFull) return fail(YCRDT_E_CAPACITY, "too many updates");
+  HIPCHK(hipSetDevice(e->device));
+  ycrdt_batch& b = scratch_batch(e);  // engine-owned: no hipMalloc / hipFree per call
+  int rc = stage(&b, ups, n, nullptr, 0);
+  if (rc) return rc;
+  if (b.nwin > 1) return fail(YCRDT_E_CAPACITY, "state vectors of more than 4 GiB of updates");
+  Work& w = e->w;
+  w.lz_multi = 0;
+  w.capped = 0;
+  w.ds_first = e->compat == 135 ? 1u : 0u;
+  e->ws_owner = nullptr;
+  auto& V = e->bufs;
+  g_bufs = &V;
+  hipStream_t s = e->stream;
+  Decoded D;
+  if ((rc = run_decode(e, &b, true, D))) return rc;
+  const uint32_t nu = (uint32_t)n;
+  bool ok = true;
+  StoreSv A{};
+  A.nstructs = D.nstructs;
+  A.nsections = D.nsections;
+  A.out_cap = store_sv_bound(nu, D.nsections);
+  A.sec_skip = take<uint32_t>(V, B_STSKIP, (size_t)D.nsections + 1, ok);
+  A.size = take<uint32_t>(V, B_STSIZE, (size_t)nu + 2, ok);
+  A.offs = take<uint64_t>(V, B_STOFFS, (size_t)nu + 2, ok);
+  A.out = take<uint8_t>(V, B_STOUT, A.out_cap + 16, ok);
+  if (!ok) return fail(YCRDT_E_DEVICE, oom("state vectors from updates"));
+  mark(e, "store.sv");
+  launch_update_svs(w, A, s);
+  mark(e, "end");
+  HIPCHK(hipEventRecord(e->ev1, s));
+  HIPCHK(hipMemcpyAsync(offs, A.offs, sizeof(uint64_t) * ((size_t)nu + 1), hipMemcpyDeviceToHost, s));
+  Counters c;
+  if ((rc = check(e, c, "state vectors from updates"))) { offs[0] = 0; return rc; }
+  collect_phase_ms(e);
+  const uint64_t total = offs[nu];
+  if (total > A.out_cap) { offs[0] = 0; return fail(YCRDT_E_DEVICE, "internal: state vectors past their bound"); }
+  uint8_t* dst = (uint8_t*)malloc(total ? total : 1);
+  if (!dst) { offs[0] = 0; return fail(YCRDT_E_CAPACITY, "host allocation failed"); }
+  if ((rc = d2h_span(e, dst, A.out, total)) || hipStreamSynchronize(s) != hipSuccess) {
+    free(dst);
+    offs[0] = 0;
+    return rc ? rc : fail(YCRDT_E_DEVICE, "HIP error (state vectors from updates)");
+  }
+  float ms = 0;
+  hipEventElapsedTime(&ms, e->ev0, e->ev1);
+  blob->ptr = dst;
+  blob->len = total;
+  S.groups_device = n;
+  S.out_bytes = total;
+  S.device_ms = ms;
+  if (st) *st = S;
+  return YCRDT_OK;
+}
+
+// Y.mergeUpdates per group. Groups of 0 or 1 update are answered here; groups the batched pass does
+// not take (more than LZ_KMAX updates, compat 135, YCRDT_STORE=0, or — found on the device — a
+// non-canonical update) go through ycrdt_merge_updates one by one; the rest are staged as ONE
+// multi-document batch (document = group, updates in input order) and merged in one pass.
+int ycrdt_merge_updates_groups(ycrdt_engine* e, const ycrdt_buf* ups, const uint32_t* group_of, size_t n, uint32_t ngroups,
+                               ycrdt_out* blob, uint64_t* offs, ycrdt_store_stats* st) {
+  if (!e || !blob || !offs || (n && (!ups || !group_of))) return fail(YCRDT_E_ARG, "null arg");
+  blob->ptr = nullptr;
+  blob->len = 0;
+  offs[0] = 0;
+  ycrdt_store_stats S{};
+  if (st) *st = S;
+  for (size_t i = 0; i < n; ++i) {
+    if (group_of[i] >= ngroups) return fail(YCRDT_E_ARG, "group index out of range at " + std::to_string(i));
+    if (ups[i].len && !ups[i].ptr) return fail(YCRDT_E_ARG, "null update at " + std::to_string(i));
+  }
+  if (ngroups == 0) {
+    blob->ptr = (uint8_t*)malloc(1);
+    if (!blob->ptr) return fail(YCRDT_E_CAPACITY, "host allocation failed");
+    return YCRDT_OK;
+  }
+  if (n >= 0x7FFFFFFFull) return fail(YCRDT_E_CAPACITY, "too many updates");
+  // the updates of every group, in input order (the reader order Yjs sees: it decides the ties)
+  std::vector<uint32_t> gstart((size_t)ngroups + 1, 0), members(n);
+  for (size_t i = 0; i < n; ++i) ++gstart[group_of[i] + 1];
+  for (uint32_t g = 0; g < ngroups; ++g) gstart[g + 1] += gstart[g];
+  {
+    std::vector<uint32_t> cur(gstart.begin(), gstart.end() - 1);
+    for (size_t i = 0; i < n; ++i) members[cur[group_of[i]]++] = (uint32_t)i;
+  }
+  enum : uint8_t { K_COPIED = 0, K_SINGLE, K_DEV };
+  const bool all_single = e->compat == 135 || env_off("YCRDT_STORE");
+  std::vector<uint8_t> kind(ngroups);
+  std::vector<uint32_t> dev_of(ngroups, NONE);  // group -> its document in the staged batch
+  uint32_t nd = 0;
+  for (uint32_t g = 0; g < ngroups; ++g) {
+    const uint32_t k = gstart[g + 1] - gstart[g];
+    kind[g] = k <= 1 ? K_COPIED : (all_single || k > LZ_KMAX) ? K_SINGLE : K_DEV;
+    if (kind[g] == K_DEV) dev_of[g] = nd++;
+  }
+  HIPCHK(hipSetDevice(e->device));
+  uint8_t* dev = nullptr;  // the batched pass's blob
+  std::vector<uint64_t> doffs;
+  std::vector<ycrdt_out> single(ngroups, ycrdt_out{nullptr, 0});
+  auto release = [&]() {
+    free(dev);
+    for (auto& o : single) ycrdt_free(&o);
+  };
+  if (nd) {
+    std::vector<ycrdt_buf> dups;
+    std::vector<uint32_t> ddoc;
+    for (size_t i = 0; i < n; ++i)
+      if (kind[group_of[i]] == K_DEV) { dups.push_back(ups[i]); ddoc.push_back(dev_of[group_of[i]]); }
+    ycrdt_batch& b = scratch_batch(e);  // engine-owned: no hipMalloc / hipFree per call
+    int rc = stage(&b, dups.data(), dups.size(), nullptr, 0, nd > 1 ? ddoc.data() : nullptr, nd);
+    std::vector<uint32_t> skip;
+    if (rc == YCRDT_OK) rc = run_lazy_groups(e, &b, &dev, doffs, skip, &S.device_ms);
+    if (rc) return rc;
+    for (uint32_t g = 0; g < ngroups; ++g)
+      if (kind[g] == K_DEV && skip[dev_of[g]]) kind[g] = K_SINGLE;  // (it holds a non-canonical update)
+  }
+  for (uint32_t g = 0; g < ngroups; ++g) {
+    if (kind[g] != K_SINGLE) continue;
+    std::vector<ycrdt_buf> gu;
+    for (uint32_t k = gstart[g]; k < gstart[g + 1]; ++k) gu.push_back(ups[members[k]]);
+    if (const int rc = ycrdt_merge_updates(e, gu.data(), gu.size(), &single[g])) { release(); return rc; }
+  }
+  static const uint8_t EMPTY[2] = {0, 0};  // what ycrdt_merge_updates gives for no update
+  auto bytes_of = [&](uint32_t g, const uint8_t*& p) -> uint64_t {
+    const uint32_t k = gstart[g + 1] - gstart[g];
+    if (kind[g] == K_DEV) { p = dev + doffs[dev_of[g]]; return doffs[dev_of[g] + 1] - doffs[dev_of[g]]; }
+    if (kind[g] == K_SINGLE) { p = single[g].ptr; return single[g].len; }
+    if (k == 0) { p = EMPTY; return 2; }
+    p = ups[members[gstart[g]]].ptr;
+    return ups[members[gstart[g]]].len;
+  };
+  uint64_t total = 0;
+  for (uint32_t g = 0; g < ngroups; ++g) {
+    const uint8_t* p;
+    offs[g] = total;
+    total += bytes_of(g, p);
+    if (kind[g] == K_DEV) ++S.groups_device; else if (kind[g] == K_SINGLE) ++S.groups_single; else ++S.groups_copied;
+  }
+  offs[ngroups] = total;
+  if (S.groups_device == ngroups) {  // every group came from the batched pass, in order: its blob is the result
+    blob->ptr = dev;
+    dev = nullptr;
+  } else {
+    blob->ptr = (uint8_t*)malloc(total ? total : 1);
+    if (!blob->ptr) { release(); offs[0] = 0; return fail(YCRDT_E_CAPACITY, "host allocation failed"); }
+    for (uint32_t g = 0; g < ngroups; ++g) {
+      const uint8_t* p;
+      const uint64_t len = bytes_of(g, p);
+      if (len) memcpy(blob->ptr + offs[g], p, len);
+    }
+  }
+  blob->len = total;
+  release();
+  S.out_bytes = total;
+  if (st) *st = S;
+  return YCRDT_OK;
+}
+
+int ycrdt_update_state_vector(ycrdt_engine* e, ycrdt_buf update, ycrdt_out* out) {
+  if (!e || !out) return fail(YCRDT_E_ARG, "null arg");
+  out->ptr = nullptr;
+  out->len = 0;
+  uint64_t offs[2] = {0, 0};
+  return ycrdt_updates_state_vectors(e, &update, 1, out, offs, nullptr);
 }
 
 void ycrdt_batch_destroy(ycrdt_batch* b) {

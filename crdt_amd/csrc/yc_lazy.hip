@@ -24,7 +24,6 @@
 
 namespace yc {
 
-constexpr uint32_t LZ_KMAX = 1024;  // readers (updates) per client handled in LDS
 constexpr uint32_t END = NONE;
 
 // ---------------------------------------------------------------- section order / reader runs
@@ -73,6 +72,12 @@ __global__ void k_lz_cap(Work w, uint32_t nclients) {
   w.lz_cap[r] = 2 * tot + 2;
 }
 
+// groups mode (a multi-document batch, document = group): the client table is keyed (group, client),
+// so rank r = nclients - 1 - cidx runs over (group descending, client descending)
+__device__ __forceinline__ uint32_t lz_group_of_rank(const Work& w, uint32_t nclients, uint32_t r) {
+  return w.udoc ? w.cl_doc[nclients - 1 - r] : 0u;
+}
+
 // ---------------------------------------------------------------- the per-client lazy merge
 struct Cur {
   uint32_t kind;   // REF_GC, REF_SKIP or 1 (item)
@@ -90,6 +95,14 @@ __global__ __launch_bounds__(64) void k_lz_merge(Work w, uint32_t nclients, unsi
   const uint32_t a = w.lz_rstart[r], K = w.lz_rstart[r + 1] - a;
   const uint32_t base = w.lz_evbase[r];
   const uint32_t cap = w.lz_cap[r];
+  // groups mode: a group that holds a non-canonical update is left to the caller. Its readers could
+  // look back to a LOWER client's workgroup (a higher rank, perhaps not started): none of its
+  // workgroups waits, each writes no event and publishes its sections' flags.
+  if (w.sg_skip && w.sg_skip[lz_group_of_rank(w, nclients, r)]) {
+    if (lane == 0) w.lz_evn[r] = 0;
+    for (uint32_t k = lane; k < K; k += 64) __hip_atomic_store(&w.lz_flag[w.lz_sec[a + k]], 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+    return;
+  }
   bool fail = K > LZ_KMAX;
   if (fail && lane == 0) raise_err(&w.ctr->err, ERR_CAPACITY);
   // ---- readers: first struct + arrival stamp (look back to the previous section's wave)
@@ -520,6 +533,14 @@ __device__ uint32_t blk_section_n(const Work& w, uint32_t b) {  // structs of th
   }
   return n;
 }
+// groups mode: block b's bytes lie behind its group's block count, at the group's offset in `out`
+// (the batch-wide blk_pos runs over all groups; mod 2^32, the sum with blk_pos[b] is exact)
+__device__ __forceinline__ uint32_t lz_group_shift(const Work& w, uint32_t b) {
+  if (!w.sg) return 0u;
+  const uint32_t g = lz_group_of_rank(w, w.lz_nblk, b);
+  const LzGroup G = w.sg[g];
+  return (uint32_t)w.sg_offs[g] + vu_size(G.nheads) - w.blk_pos[G.b0];
+}
 // event slots [evbase[b], evbase[b] + cap[b]); slots past evn[b] are empty
 __global__ __launch_bounds__(256) void k_ev_sizes(Work w, uint32_t nslots) {
   const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
@@ -553,7 +574,7 @@ __global__ __launch_bounds__(256) void k_ev_write(Work w, uint32_t nslots) {
   const uint32_t client = blk_client(w, b);
   const uint32_t hdr = blk_continues(w, b) ? 0u : vu_size(blk_section_n(w, b)) + vu_size(client) + vu_size(w.ev_clock[e0]);
   const uint32_t hoff = w.lz_multi ? 0u : vu_size(w.ctr->pad[0]);  // lz_multi: the host writes per-update headers
-  const uint32_t p = hoff + w.blk_pos[b] + hdr + (w.ev_pos[e] - w.ev_pos[e0]);
+  const uint32_t p = hoff + w.blk_pos[b] + lz_group_shift(w, b) + hdr + (w.ev_pos[e] - w.ev_pos[e0]);
   encode_event<true>(w, client, e, w.out, p);
 }
 __global__ void k_blk_write(Work w, uint32_t nblk) {
@@ -562,7 +583,7 @@ __global__ void k_blk_write(Work w, uint32_t nblk) {
   if (b >= nblk) return;
   const uint32_t n = w.lz_evn[b];
   if (!n || blk_continues(w, b)) return;
-  uint32_t p = (w.lz_multi ? 0u : vu_size(w.ctr->pad[0])) + w.blk_pos[b];
+  uint32_t p = (w.lz_multi ? 0u : vu_size(w.ctr->pad[0])) + w.blk_pos[b] + lz_group_shift(w, b);
   p = wr_vu(w.out, p, blk_section_n(w, b));
   p = wr_vu(w.out, p, blk_client(w, b));
   wr_vu(w.out, p, w.ev_clock[w.lz_evbase[b]]);
@@ -788,6 +809,188 @@ void launch_lazy_write(Work& w, uint32_t nslots, uint32_t nr, uint32_t dsbase, h
     hipMemcpyAsync(w.out + dsbase, &zero, 1, hipMemcpyHostToDevice, s);
     hipStreamSynchronize(s);
   }
+}
+
+// ---------------------------------------------------------------- groups mode
+// ycrdt_merge_updates_groups: one Y.mergeUpdates per group, many groups in one pass. The batch is
+// staged as a multi-document batch (document = group), so the client table is keyed (group, client)
+// and k_lz_merge's ranks run over (group desc, client desc): a group's client blocks are one
+// contiguous range of ranks, and two groups never share a block, whatever client ids they share.
+// Look-back: k_lz_merge waits on lz_prev, the previous non-empty section of the same update. In a
+// canonical update that section names a HIGHER client of the SAME group, hence a lower rank, hence
+// a workgroup ordered_block_id has already started. A group that holds a non-canonical update
+// (k_lg_canon) breaks exactly this and is left out (sg_skip).
+// Delete sets: the 64-bit sort key (~client, clock) has no room for the group, so the stable sort
+// runs twice — by (~client, clock), then by group — and the run logic segments by a dense
+// (group, client) id, so ranges of one client id in two groups neither merge nor share a
+// writeDeleteSet client group.
+// Output: group g = [varuint blocks][blocks][varuint delete-set clients][delete-set groups] at
+// out + sg_offs[g]; sizes, offsets and the headers are computed and written here.
+__global__ void k_lg_canon(Work w) {
+  const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
+  if (u >= w.nupd) return;
+  const uint32_t a = w.usec_start[u], b = a + w.usec_n[u];
+  bool canon = true;
+  for (uint32_t i = a + 1; i < b && canon; ++i) canon = w.sections[i].client < w.sections[i - 1].client;
+  if (!canon) w.sg_skip[doc_of_update(w, u)] = 1u;
+}
+__global__ void k_lg_ds_keys(Work w, uint32_t nds) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nds) return;
+  const DsRange d = w.ds[i];
+  w.dsm_key[i] = ((uint64_t)(~d.client) << 32) | d.clock;
+  w.dsm_len[i] = i;
+}
+// second sort key: the group of the range at sorted position p (dsm_lens[p] = its index in ds)
+__global__ void k_lg_ds_gkeys(Work w, uint32_t nds) {
+  const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= nds) return;
+  w.dsm_key[p] = doc_of_update(w, w.ds[w.dsm_lens[p]].upd);
+  w.dsm_len[p] = p;
+}
+// rows in (group asc, client desc, clock asc) order: key and length in dsm_key / dsm_len, group in rgrp
+__global__ void k_lg_ds_gather(Work w, uint32_t nds, uint32_t* __restrict__ rgrp) {
+  const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= nds) return;
+  const uint32_t q = w.dsm_rid[p];
+  w.dsm_key[p] = w.dsm_keys[q];
+  w.dsm_len[p] = w.ds[w.dsm_lens[q]].len;
+  rgrp[p] = (uint32_t)w.dsm_end[p];
+}
+__global__ void k_lg_ds_heads(Work w, uint32_t nds, const uint32_t* __restrict__ rgrp) {
+  const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p > nds) return;
+  w.dsm_flag[p] = (p < nds && (p == 0 || rgrp[p] != rgrp[p - 1] || (w.dsm_key[p] >> 32) != (w.dsm_key[p - 1] >> 32))) ? 1u : 0u;
+}
+// (dense (group, client) id, range end): the running max restarts where the id changes
+__global__ void k_lg_ds_ends(Work w, uint32_t nds) {
+  const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= nds) return;
+  const uint32_t seg = w.dsm_rid[p] + w.dsm_flag[p] - 1;
+  w.dsm_end[p] = ((uint64_t)seg << 32) | (uint64_t)((uint32_t)w.dsm_key[p] + w.dsm_len[p]);
+}
+__global__ void k_lg_ds_flags(Work w, uint32_t nds) {
+  const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p > nds) return;
+  if (p == nds) { w.dsm_flag[p] = 0; return; }
+  const bool st = p == 0 || (w.dsm_end[p - 1] >> 32) != (w.dsm_end[p] >> 32) || (uint32_t)w.dsm_max[p - 1] < (uint32_t)w.dsm_key[p];
+  w.dsm_flag[p] = st ? 1u : 0u;
+}
+__global__ void k_lg_ds_runs(Work w, uint32_t nds, const uint32_t* __restrict__ rgrp) {
+  const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= nds) return;
+  const uint32_t rid = w.dsm_rid[p] + w.dsm_flag[p] - 1;
+  const uint64_t k = w.dsm_key[p];
+  if (w.dsm_flag[p]) {
+    w.dr_client[rid] = ~(uint32_t)(k >> 32);
+    w.dr_clock[rid] = (uint32_t)k;
+    w.dr_group[rid] = rgrp[p];
+  }
+  if (p + 1 == nds || w.dsm_flag[p + 1]) w.dr_end[rid] = (uint32_t)w.dsm_max[p];
+}
+__global__ void k_lg_dw_flags(Work w, uint32_t nr) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i > nr) return;
+  w.dw_flag[i] = (i < nr && (i == 0 || w.dr_group[i] != w.dr_group[i - 1] || w.dr_client[i] != w.dr_client[i - 1])) ? 1u : 0u;
+}
+__global__ void k_lg_heads(Work w, uint32_t nblk, uint32_t* __restrict__ hflag) {
+  const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b > nblk) return;
+  hflag[b] = (b < nblk && w.lz_evn[b]) ? 1u : 0u;
+}
+__global__ void k_lg_layout(Work w, uint32_t nr) {
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g > w.ndocs) return;
+  if (g == w.ndocs) { w.sg_size[g] = 0; return; }
+  const uint32_t nblk = w.lz_nblk;
+  uint32_t lo = 0, hi = nblk;
+  if (w.udoc) { lo = lower_bound_u32(w.cl_doc, nblk, g); hi = upper_bound_u32(w.cl_doc, nblk, g); }
+  LzGroup G;
+  G.b0 = nblk - hi;
+  G.b1 = nblk - lo;
+  G.r0 = nr ? lower_bound_u32(w.dr_group, nr, g) : 0u;
+  G.r1 = nr ? upper_bound_u32(w.dr_group, nr, g) : 0u;
+  G.nheads = nblk ? w.sg_hpre[G.b1] - w.sg_hpre[G.b0] : 0u;
+  G.blk_bytes = nblk ? w.blk_pos[G.b1] - w.blk_pos[G.b0] : 0u;
+  G.ng = nr ? w.dw_gid[G.r1] - w.dw_gid[G.r0] : 0u;
+  G.ds_bytes = nr ? w.dw_pos[G.r1] - w.dw_pos[G.r0] : 0u;
+  w.sg[g] = G;
+  const uint64_t size = (uint64_t)vu_size(G.nheads) + G.blk_bytes + vu_size(G.ng) + G.ds_bytes;
+  if (size > 0xFFFFFFF0ull) raise_err(&w.ctr->err, ERR_CAPACITY);
+  w.sg_size[g] = w.sg_skip[g] ? 0u : (uint32_t)size;
+}
+__global__ void k_lg_headers(Work w) {
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= w.ndocs || w.sg_skip[g]) return;
+  const LzGroup G = w.sg[g];
+  uint32_t p = wr_vu(w.out, (uint32_t)w.sg_offs[g], G.nheads);
+  wr_vu(w.out, p + G.blk_bytes, G.ng);
+}
+__global__ void k_lg_dw_write(Work w, uint32_t nr) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nr) return;
+  const uint32_t g = w.dr_group[i];
+  if (w.sg_skip[g]) return;
+  const LzGroup G = w.sg[g];
+  uint32_t p = (uint32_t)w.sg_offs[g] + vu_size(G.nheads) + G.blk_bytes + vu_size(G.ng) + (w.dw_pos[i] - w.dw_pos[G.r0]);
+  if (w.dw_flag[i]) {
+    const uint32_t gi = w.dw_gid[i];
+    p = wr_vu(w.out, p, w.dr_client[i]);
+    p = wr_vu(w.out, p, w.dw_gstart[gi + 1] - w.dw_gstart[gi]);
+  }
+  const uint32_t clock = w.dr_clock[i];
+  p = wr_vu(w.out, p, clock);
+  wr_vu(w.out, p, w.dr_end[i] - clock);
+}
+
+// which groups hold a non-canonical update (before launch_lazy_merge reads sg_skip)
+void launch_groups_canon(Work& w, hipStream_t s) {
+  hipMemsetAsync(w.sg_skip, 0, sizeof(uint32_t) * (w.ndocs + 1), s);
+  if (w.nupd) hipLaunchKernelGGL(k_lg_canon, dim3(G(w.nupd)), dim3(256), 0, s, w);
+}
+// the groups' delete-set runs in (group asc, client desc, clock asc) order; returns their count
+uint32_t launch_groups_ds_runs(Work& w, uint32_t nds, hipStream_t s) {
+  if (!nds) return 0;
+  uint32_t* rgrp = w.dw_size;  // (free until k_dw_sizes)
+  hipLaunchKernelGGL(k_lg_ds_keys, dim3(G(nds)), dim3(256), 0, s, w, nds);
+  sort_pairs_u64_u32(w.tmp, w.tmp_bytes, w.dsm_key, w.dsm_keys, w.dsm_len, w.dsm_lens, nds, s);
+  hipLaunchKernelGGL(k_lg_ds_gkeys, dim3(G(nds)), dim3(256), 0, s, w, nds);
+  sort_pairs_u64_u32(w.tmp, w.tmp_bytes, w.dsm_key, w.dsm_end, w.dsm_len, w.dsm_rid, nds, s, 32);
+  hipLaunchKernelGGL(k_lg_ds_gather, dim3(G(nds)), dim3(256), 0, s, w, nds, rgrp);
+  hipLaunchKernelGGL(k_lg_ds_heads, dim3(G(nds + 1)), dim3(256), 0, s, w, nds, rgrp);
+  scan_u32(w.tmp, w.tmp_bytes, w.dsm_flag, w.dsm_rid, nds + 1, s);
+  hipLaunchKernelGGL(k_lg_ds_ends, dim3(G(nds)), dim3(256), 0, s, w, nds);
+  scan_segmax_u64(w.tmp, w.tmp_bytes, w.dsm_end, w.dsm_max, nds, s);
+  hipLaunchKernelGGL(k_lg_ds_flags, dim3(G(nds + 1)), dim3(256), 0, s, w, nds);
+  scan_u32(w.tmp, w.tmp_bytes, w.dsm_flag, w.dsm_rid, nds + 1, s);
+  hipLaunchKernelGGL(k_lg_ds_runs, dim3(G(nds)), dim3(256), 0, s, w, nds, rgrp);
+  uint32_t nr = 0;
+  hipMemcpyAsync(&nr, w.dsm_rid + nds, sizeof(uint32_t), hipMemcpyDeviceToHost, s);
+  hipStreamSynchronize(s);
+  return nr;
+}
+// delete-set sizes, the groups' ranges and sizes, their offsets (sg_offs[ndocs] = the total)
+void launch_groups_layout(Work& w, uint32_t nr, hipStream_t s) {
+  if (nr) {
+    hipLaunchKernelGGL(k_lg_dw_flags, dim3(G(nr + 1)), dim3(256), 0, s, w, nr);
+    scan_u32(w.tmp, w.tmp_bytes, w.dw_flag, w.dw_gid, nr + 1, s);
+    hipLaunchKernelGGL(k_dw_gstart, dim3(G(nr)), dim3(256), 0, s, w, nr);
+    hipLaunchKernelGGL(k_dw_sizes, dim3(G(nr + 1)), dim3(256), 0, s, w, nr);
+    scan_u32(w.tmp, w.tmp_bytes, w.dw_size, w.dw_pos, nr + 1, s);
+  }
+  if (w.lz_nblk) {
+    uint32_t* hflag = w.lz_cap;  // (free after the merge)
+    hipLaunchKernelGGL(k_lg_heads, dim3(G(w.lz_nblk + 1)), dim3(256), 0, s, w, w.lz_nblk, hflag);
+    scan_u32(w.tmp, w.tmp_bytes, hflag, w.sg_hpre, w.lz_nblk + 1, s);
+  }
+  hipLaunchKernelGGL(k_lg_layout, dim3(G(w.ndocs + 1)), dim3(256), 0, s, w, nr);
+  scan_u32_to_u64(w.tmp, w.tmp_bytes, w.sg_size, w.sg_offs, (uint64_t)w.ndocs + 1, s);
+}
+void launch_groups_write(Work& w, uint32_t nslots, uint32_t nr, hipStream_t s) {
+  hipLaunchKernelGGL(k_lg_headers, dim3(G(w.ndocs)), dim3(256), 0, s, w);
+  if (w.lz_nblk) hipLaunchKernelGGL(k_blk_write, dim3(G(w.lz_nblk)), dim3(256), 0, s, w, w.lz_nblk);
+  if (nslots) hipLaunchKernelGGL(k_ev_write, dim3(G(nslots)), dim3(256), 0, s, w, nslots);
+  if (nr) hipLaunchKernelGGL(k_lg_dw_write, dim3(G(nr)), dim3(256), 0, s, w, nr);
 }
 
 }  // namespace yc

@@ -77,6 +77,17 @@ __host__ __device__ inline uint64_t win_use(uint32_t shift) {
   return (1ull << shift) - (shift >= 28 ? (1ull << 20) : (1ull << 12));
 }
 
+// Groups mode of the lazy merge (ycrdt_merge_updates_groups): where group g's client blocks and
+// delete-set runs lie in the batch-wide tables, and what its two varuint headers say
+struct LzGroup {
+  uint32_t b0, b1;      // its client blocks (ranks)
+  uint32_t r0, r1;      // its delete-set runs
+  uint32_t nheads;      // non-empty client blocks
+  uint32_t ng;          // delete-set client groups
+  uint32_t blk_bytes;   // bytes of its blocks
+  uint32_t ds_bytes;    // bytes of its delete-set groups
+};
+
 struct Work {
   // ---- batch input
   const uint8_t* bytes = nullptr;  // every update starts at a 64-byte aligned offset of its window
@@ -297,6 +308,13 @@ struct Work {
   uint32_t lz_nblk = 0, lz_diff = 0;
   uint32_t lz_multi = 0;            // 1: one diffUpdate per input update (sync responder batch); no global headers
   uint32_t* lz_bclient = nullptr;   // serial lazy merge: client of every output section (null: per-client blocks)
+  // groups mode: one mergeUpdates per document (= group) of a multi-document batch, null otherwise
+  LzGroup* sg = nullptr;            // [ndocs]
+  uint64_t* sg_offs = nullptr;      // [ndocs + 1] byte offset of every group's output in `out`
+  uint32_t* sg_size = nullptr;      // [ndocs + 1] its bytes
+  uint32_t* sg_skip = nullptr;      // [ndocs] 1: the group holds a non-canonical update and is left out (the caller merges it alone)
+  uint32_t* sg_hpre = nullptr;      // [blocks + 1] non-empty blocks in front of every block
+  uint32_t* dr_group = nullptr;     // [runs] group of every delete-set run
   uint32_t* ev_kind = nullptr;     // [slots] REF_GC | REF_SKIP | 1 (item)
   uint32_t* ev_src = nullptr;
   uint32_t* ev_clock = nullptr;
@@ -845,5 +863,11 @@ uint32_t launch_event_sizes(Work& w, hipStream_t s, uint32_t* nslots_out);
 uint32_t launch_ds_runs(Work& w, uint32_t nds, bool merge, hipStream_t s);
 uint32_t launch_ds_write_sizes(Work& w, uint32_t nr, hipStream_t s);
 void launch_lazy_write(Work& w, uint32_t nslots, uint32_t nr, uint32_t dsbase, hipStream_t s);
+// groups mode (one mergeUpdates per document of a multi-document batch; w.sg* set by the caller)
+constexpr uint32_t LZ_KMAX = 1024;  // readers (updates) per client k_lz_merge handles in LDS
+void launch_groups_canon(Work& w, hipStream_t s);                        // sg_skip: groups holding a non-canonical update
+uint32_t launch_groups_ds_runs(Work& w, uint32_t nds, hipStream_t s);    // delete-set runs per group; their count
+void launch_groups_layout(Work& w, uint32_t nr, hipStream_t s);          // sizes, sg, sg_offs (sg_offs[ndocs]: total bytes)
+void launch_groups_write(Work& w, uint32_t nslots, uint32_t nr, hipStream_t s);  // headers, blocks, delete sets into w.out
 
 }  // namespace yc

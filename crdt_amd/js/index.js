@@ -8,7 +8,8 @@
 //   YMap set / get / has / delete / toJSON / observe / unobserve,
 //   YArray insert / push / unshift / delete / toJSON / toArray / length / observe / unobserve,
 //   Y.applyUpdate, Y.encodeStateAsUpdate(doc[, sv]), Y.encodeStateVector, Y.mergeUpdates,
-//   Y.diffUpdate, plus the batch entries Y.applyUpdates (one doc) and Y.applyUpdatesMulti (a fleet).
+//   Y.diffUpdate, Y.encodeStateVectorFromUpdate, plus the batch entries Y.applyUpdates (one doc),
+//   Y.applyUpdatesMulti (a fleet), Y.mergeUpdatesGroups and Y.encodeStateVectorsFromUpdates.
 // Every local op is written by the engine as the Yjs v1 struct a Yjs doc would create, so the
 // doc's bytes stay identical to Yjs's (tests/js/napi_check.js `ops`). Values go through the
 // lib0 `any` codec (any.js). toJSON reads the device-materialised view (map winners, list order).
@@ -344,6 +345,13 @@ module.exports = {
   // batch entry (not in Yjs): [Y.diffUpdate(u, sv) for each pair] in one device pass — the sync
   // responder (crdt.js:286-291) answering many joining peers / topics at once
   diffUpdates: (updates, svs) => binding.diffUpdates(updates, svs),
+  // the doc-less update store (persistence without docs, INTEGRATION.md): what a store holds of a
+  // topic, from its update bytes alone (crdt.js:28-77 builds two temporary docs for this)
+  encodeStateVectorFromUpdate: (update) => binding.encodeStateVectorFromUpdate(update),
+  // batch entries (not in Yjs): the state vectors of many updates, and Y.mergeUpdates of many
+  // groups (one per topic: the logs crdt.js:79-98 replays and never compacts), one device pass each
+  encodeStateVectorsFromUpdates: (updates) => binding.encodeStateVectorsFromUpdates(updates),
+  mergeUpdatesGroups: (groups) => binding.mergeUpdatesGroups(groups),
   // opt-in incremental local-op encode (not in Yjs): the doc's local ops since the previous call as
   // one update, instead of re-encoding the whole doc after every op (crdt.js:347,383,443,...)
   takeLocalUpdate: (doc) => binding.takeLocalUpdate(doc._h),

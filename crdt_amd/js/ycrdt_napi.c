@@ -435,6 +435,124 @@ static napi_value js_diff_updates(napi_env env, napi_callback_info info) {
   return arr;
 }
 
+/* a blob and its n + 1 offsets → Uint8Array[n], views of one ArrayBuffer (releases both) */
+static napi_value slices_from_blob(napi_env env, ycrdt_out *blob, uint64_t *offs, uint32_t n) {
+  napi_value ab, arr;
+  void *data = NULL;
+  if (napi_create_arraybuffer(env, blob->len, &data, &ab) != napi_ok) {
+    ycrdt_free(blob);
+    free(offs);
+    napi_throw_error(env, NULL, "ycrdt: N-API call failed: napi_create_arraybuffer");
+    return NULL;
+  }
+  if (blob->len) memcpy(data, blob->ptr, blob->len);
+  ycrdt_free(blob);
+  napi_create_array_with_length(env, n, &arr);
+  for (uint32_t i = 0; i < n; ++i) {
+    napi_value ta;
+    napi_create_typedarray(env, napi_uint8_array, (size_t)(offs[i + 1] - offs[i]), ab, (size_t)offs[i], &ta);
+    napi_set_element(env, arr, i, ta);
+  }
+  free(offs);
+  return arr;
+}
+
+/* encodeStateVectorFromUpdate(update) → Uint8Array   (Y.encodeStateVectorFromUpdate: what a doc-less
+ * store holds of a topic, crdt.js:28-77 without the temporary doc) */
+static napi_value js_update_state_vector(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1];
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  ycrdt_buf u;
+  if (argc < 1 || !get_bytes(env, argv[0], &u)) {
+    napi_throw_type_error(env, NULL, "encodeStateVectorFromUpdate(update)");
+    return NULL;
+  }
+  ycrdt_engine *e = engine(env);
+  if (!e) return NULL;
+  ycrdt_out o = {NULL, 0};
+  int rc = ycrdt_update_state_vector(e, u, &o);
+  if (rc != YCRDT_OK) return throw_rc(env, rc);
+  return u8_from_out(env, &o);
+}
+
+/* encodeStateVectorsFromUpdates(update[]) → Uint8Array[]   (n x Y.encodeStateVectorFromUpdate in one
+ * device pass; the results are views of one ArrayBuffer) */
+static napi_value js_updates_state_vectors(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1];
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  ycrdt_buf *ups = NULL;
+  uint32_t n = 0;
+  if (argc < 1 || !get_buf_array(env, argv[0], &ups, &n)) {
+    napi_throw_type_error(env, NULL, "encodeStateVectorsFromUpdates(updates[])");
+    return NULL;
+  }
+  ycrdt_engine *e = engine(env);
+  if (!e) { free(ups); return NULL; }
+  uint64_t *offs = (uint64_t *)calloc((size_t)n + 1, sizeof(uint64_t));
+  if (!offs) {
+    free(ups);
+    napi_throw_error(env, NULL, "ycrdt: out of memory");
+    return NULL;
+  }
+  ycrdt_out blob = {NULL, 0};
+  int rc = ycrdt_updates_state_vectors(e, ups, n, &blob, offs, NULL);
+  free(ups);
+  if (rc != YCRDT_OK) { free(offs); return throw_rc(env, rc); }
+  return slices_from_blob(env, &blob, offs, n);
+}
+
+/* mergeUpdatesGroups(update[][]) → Uint8Array[]   (Y.mergeUpdates of every group in one device pass:
+ * compacting the logs of many topics, crdt.js:79-98) */
+static napi_value js_merge_updates_groups(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1];
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  bool is_arr = false;
+  if (argc > 0) napi_is_array(env, argv[0], &is_arr);
+  if (!is_arr) { napi_throw_type_error(env, NULL, "mergeUpdatesGroups(groups[][])"); return NULL; }
+  uint32_t ng = 0;
+  napi_get_array_length(env, argv[0], &ng);
+  size_t n = 0, cap = 16;
+  ycrdt_buf *ups = (ycrdt_buf *)malloc(cap * sizeof(ycrdt_buf));
+  uint32_t *gof = (uint32_t *)malloc(cap * sizeof(uint32_t));
+  for (uint32_t g = 0; g < ng && ups && gof; ++g) {
+    napi_value el;
+    ycrdt_buf *gu = NULL;
+    uint32_t k = 0;
+    napi_get_element(env, argv[0], g, &el);
+    if (!get_buf_array(env, el, &gu, &k)) {
+      free(ups);
+      free(gof);
+      napi_throw_type_error(env, NULL, "mergeUpdatesGroups: every group is an array of Uint8Arrays");
+      return NULL;
+    }
+    if (n + k > cap) {
+      while (n + k > cap) cap *= 2;
+      ups = (ycrdt_buf *)realloc(ups, cap * sizeof(ycrdt_buf));
+      gof = (uint32_t *)realloc(gof, cap * sizeof(uint32_t));
+    }
+    for (uint32_t i = 0; i < k && ups && gof; ++i) { ups[n] = gu[i]; gof[n++] = g; }
+    free(gu);
+  }
+  uint64_t *offs = (uint64_t *)calloc((size_t)ng + 1, sizeof(uint64_t));
+  ycrdt_engine *e = ups && gof && offs ? engine(env) : NULL;
+  if (!e) {
+    if (!(ups && gof && offs)) napi_throw_error(env, NULL, "ycrdt: out of memory");
+    free(ups);
+    free(gof);
+    free(offs);
+    return NULL;
+  }
+  ycrdt_out blob = {NULL, 0};
+  int rc = ycrdt_merge_updates_groups(e, ups, gof, n, ng, &blob, offs, NULL);
+  free(ups);
+  free(gof);
+  if (rc != YCRDT_OK) { free(offs); return throw_rc(env, rc); }
+  return slices_from_blob(env, &blob, offs, ng);
+}
+
 static napi_value js_version(napi_env env, napi_callback_info info) {
   (void)info;
   napi_value s;
@@ -798,6 +916,9 @@ static napi_value init(napi_env env, napi_value exports) {
       {"mergeUpdates", NULL, js_merge_updates, NULL, NULL, NULL, napi_default, NULL},
       {"diffUpdate", NULL, js_diff_update, NULL, NULL, NULL, napi_default, NULL},
       {"diffUpdates", NULL, js_diff_updates, NULL, NULL, NULL, napi_default, NULL},
+      {"encodeStateVectorFromUpdate", NULL, js_update_state_vector, NULL, NULL, NULL, napi_default, NULL},
+      {"encodeStateVectorsFromUpdates", NULL, js_updates_state_vectors, NULL, NULL, NULL, napi_default, NULL},
+      {"mergeUpdatesGroups", NULL, js_merge_updates_groups, NULL, NULL, NULL, napi_default, NULL},
       {"encodeStatesAsUpdates", NULL, js_encode_states_as_updates, NULL, NULL, NULL, napi_default, NULL},
       {"takeLocalUpdate", NULL, js_take_local_update, NULL, NULL, NULL, napi_default, NULL},
       {"trackLocalUpdates", NULL, js_track_local, NULL, NULL, NULL, napi_default, NULL},

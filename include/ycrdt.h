@@ -183,6 +183,53 @@ int ycrdt_diff_update(ycrdt_engine *e, ycrdt_buf update, ycrdt_buf sv, ycrdt_out
  * update or state vector fails the whole batch (no output is produced). */
 int ycrdt_diff_updates(ycrdt_engine *e, const ycrdt_buf *updates, const ycrdt_buf *svs, size_t n, ycrdt_out *outs);
 
+/* ---- the doc-less update store ------------------------------------------------------------
+ * A persistence worker that keeps every topic as update bytes and never builds a Y.Doc (the Yjs
+ * update API: mergeUpdates / encodeStateVectorFromUpdate / diffUpdate). crdt.js does this work with
+ * throw-away docs: storeUpdate (crdt.js:28-77) builds two temporary docs, applies twice and encodes
+ * a state vector for every stored message; getYDoc (crdt.js:79-98) replays a log that is never
+ * compacted. */
+typedef struct {
+  uint64_t groups_device;  /* answered in the batched device pass */
+  uint64_t groups_single;  /* went through the single call, one by one */
+  uint64_t groups_copied;  /* 0 or 1 update: answered on the host (1 update = returned unchanged, as Yjs) */
+  uint64_t out_bytes;
+  double device_ms;
+} ycrdt_store_stats;
+/* Y.mergeUpdates per group, many groups in ONE device pass: compacting the logs of many topics at
+ * once (the log getYDoc replays, crdt.js:79-98, is never compacted; storeUpdate, crdt.js:28-77,
+ * merges per message through two temporary docs). Update i belongs to group group_of[i] < ngroups;
+ * groups may interleave in the input, and a group's updates keep their input order (the reader
+ * order Yjs sees: it decides the ties). Group g's result = blob[offs[g] .. offs[g+1]), byte-identical
+ * to ycrdt_merge_updates over that group's updates; offs holds ngroups+1 entries; blob is released
+ * with ycrdt_free. A group with no update gives the empty update (00 00, what ycrdt_merge_updates
+ * gives for n == 0); a group of one update is returned unchanged, as Yjs does, even when that
+ * update is not canonical (both: groups_copied). The other groups are staged as one multi-document
+ * batch and merged in one pass — sizes, offsets and the per-group varuint headers computed and
+ * written on the device, one copy back — except those that take
+ * ycrdt_merge_updates one by one (groups_single; its error, if any, is returned): a group holding
+ * an update whose sections are not in strictly descending client order, a group of more than 1024
+ * updates, every group of an engine with compat 135, and every group when YCRDT_STORE=0 is set.
+ * groups_device + groups_single + groups_copied == ngroups. group_of[i] >= ngroups gives
+ * YCRDT_E_ARG; a malformed update fails the whole call with YCRDT_E_DECODE and no output; more than
+ * 4 GiB staged at once is YCRDT_E_CAPACITY. ngroups == 0 needs no device. */
+int ycrdt_merge_updates_groups(ycrdt_engine *e, const ycrdt_buf *ups, const uint32_t *group_of, size_t n,
+                               uint32_t ngroups, ycrdt_out *blob, uint64_t *offs,
+                               ycrdt_store_stats *st /* may be NULL */);
+/* Y.encodeStateVectorFromUpdate(ups[i]) for n updates in ONE device pass: what a store holds of
+ * every topic, refreshed after a write (the `Y.encodeStateVector(tempDoc)` of crdt.js:28-77 without
+ * the doc). blob[offs[i] .. offs[i+1]) is Yjs's result for ups[i]; offs holds n+1 entries; blob is
+ * released with ycrdt_free. As in Yjs the pairs keep the update's own client order (not re-sorted),
+ * a client counts up to its first Skip and only when its first struct starts at clock 0,
+ * neighbouring sections of one client count as one, the delete set is not read, and the result is
+ * the same under compat 135 and 136; the empty update (00 00) gives 00. A malformed update fails
+ * the whole call with YCRDT_E_DECODE and no output. n == 0 needs no device. The stats' groups_*
+ * count updates (all of them groups_device). */
+int ycrdt_updates_state_vectors(ycrdt_engine *e, const ycrdt_buf *ups, size_t n, ycrdt_out *blob, uint64_t *offs,
+                                ycrdt_store_stats *st /* may be NULL */);
+/* the single-call form: Y.encodeStateVectorFromUpdate(update) */
+int ycrdt_update_state_vector(ycrdt_engine *e, ycrdt_buf update, ycrdt_out *out);
+
 /* ---- crdt.c materialisation and local ops ------------------------------------------------
  * A "target" is root type `root`, or (parent_key != NULL) the shared type stored in root YMap
  * `root` under `parent_key` (crdt.js nests one YArray per map key, crdt.js:423-430).
