@@ -90,6 +90,35 @@ class SyncStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class ReadStats(ctypes.Structure):
+    _fields_ = [
+        ("reads_device", ctypes.c_uint64),
+        ("reads_single", ctypes.c_uint64),
+        ("reads_empty", ctypes.c_uint64),
+        ("out_bytes", ctypes.c_uint64),
+        ("depth_max", ctypes.c_uint32),
+        ("name_max", ctypes.c_uint32),
+        ("device_ms", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class _Read(ctypes.Structure):  # ycrdt_read
+    _fields_ = [
+        ("doc", ctypes.c_void_p),
+        ("root", ctypes.c_char_p),
+        ("parent_key", ctypes.c_char_p),
+        ("key", ctypes.c_char_p),
+        ("index", ctypes.c_uint64),
+        ("op", ctypes.c_int),
+    ]
+
+
+READ_OPS = {"map_get": 0, "map_size": 1, "array_get": 2, "array_length": 3}
+
+
 class JsonStats(ctypes.Structure):
     _fields_ = [
         ("pairs_device", ctypes.c_uint64),
@@ -138,7 +167,7 @@ EXPORTS = (
     "ycrdt_comm_unique_id", "ycrdt_comm_create", "ycrdt_comm_destroy", "ycrdt_batch_merge_sharded",
     "ycrdt_comm_sv_allreduce_max", "ycrdt_comm_ds_allgather", "ycrdt_comm_create_exchange", "ycrdt_route",
     "ycrdt_comm_fleet_sv_allreduce_max", "ycrdt_docs_states_packed", "ycrdt_comm_allgather", "ycrdt_device_count",
-    "ycrdt_docs_diff", "ycrdt_docs_json",
+    "ycrdt_docs_diff", "ycrdt_docs_json", "ycrdt_docs_read",
     "ycrdt_merge_updates_groups", "ycrdt_updates_state_vectors", "ycrdt_update_state_vector",
 )
 
@@ -220,6 +249,7 @@ def lib():
     L.ycrdt_route.argtypes = [ctypes.c_char_p, sz, u32]
     L.ycrdt_docs_diff.argtypes = [vp, P(vp), P(_Buf), sz, P(_Out), P(ctypes.c_uint64), P(SyncStats)]
     L.ycrdt_docs_json.argtypes = [vp, P(vp), P(cs), P(i32), sz, P(_Out), P(ctypes.c_uint64), P(JsonStats)]
+    L.ycrdt_docs_read.argtypes = [vp, P(_Read), sz, P(_Out), P(ctypes.c_uint64), P(ctypes.c_int32), P(ctypes.c_uint64), P(ReadStats)]
     L.ycrdt_merge_updates_groups.argtypes = [vp, P(_Buf), P(u32), sz, u32, P(_Out), P(ctypes.c_uint64), P(StoreStats)]
     L.ycrdt_updates_state_vectors.argtypes = [vp, P(_Buf), sz, P(_Out), P(ctypes.c_uint64), P(StoreStats)]
     L.ycrdt_update_state_vector.argtypes = [vp, _Buf, P(_Out)]
@@ -851,6 +881,54 @@ def docs_json_stats(docs, roots, kinds, engine=None):
 def docs_json(docs, roots, kinds, engine=None) -> list:
     """[d.root_json(root, kind) for d, root, kind in zip(docs, roots, kinds)] in one device pass (docs_json_stats)."""
     return docs_json_stats(docs, roots, kinds, engine)[0]
+
+
+def docs_read_stats(reads, engine=None):
+    """(answers, stats) of many point reads in one device pass (ycrdt_docs_read): the
+    `h[name].get(key)` / `.length` reads of crdt.js:423-430 batched over documents. reads: tuples
+    (op, doc, root, key_or_index_or_None, parent_key_or_None), op "map_get" | "map_size" |
+    "array_get" | "array_length". An answer is (state, json_text) — Doc.map_get / Doc.array_get —
+    for the get ops and an int — Doc.map_size / Doc.array_length — for the others. A document may
+    repeat. stats: ycrdt_read_stats as a dict (which path the reads took)."""
+    import numpy as np
+
+    def enc(x):
+        return None if x is None else x if isinstance(x, bytes) else x.encode()
+
+    n = len(reads)
+    arr = (_Read * max(n, 1))()
+    for i, rd in enumerate(reads):
+        op, d, root, arg, pkey = (tuple(rd) + (None, None))[:5]
+        if op not in READ_OPS:
+            raise ValueError(f"docs_read: op {op!r} (\"map_get\" | \"map_size\" | \"array_get\" | \"array_length\")")
+        if (op == "map_get" and not isinstance(arg, (str, bytes))) or (op == "array_get" and not isinstance(arg, int)):
+            raise ValueError(f"docs_read: {op} needs a {'key' if op == 'map_get' else 'index'}")
+        r = arr[i]
+        r.doc, r.root, r.parent_key, r.op = d._h.value, enc(root), enc(pkey), READ_OPS[op]
+        if op == "map_get":
+            r.key = enc(arg)
+        elif op == "array_get":
+            r.index = arg
+    eng = engine or (reads[0][1].engine if n else default_engine())
+    offs = np.zeros(n + 1, dtype=np.uint64)
+    states = np.zeros(max(n, 1), dtype=np.int32)
+    counts = np.zeros(max(n, 1), dtype=np.uint64)
+    out = _Out()
+    st = ReadStats()
+    _check(lib().ycrdt_docs_read(eng._h, arr, n, ctypes.byref(out), offs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+                                 states.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                 counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ctypes.byref(st)))
+    try:
+        o, sl, cl = offs.tolist(), states.tolist(), counts.tolist()
+        blob = ctypes.string_at(out.ptr, out.len) if out.len else b""
+        return [(sl[i], blob[o[i]:o[i + 1]].decode()) if arr[i].op in (0, 2) else cl[i] for i in range(n)], st.as_dict()
+    finally:
+        lib().ycrdt_free(ctypes.byref(out))
+
+
+def docs_read(reads, engine=None) -> list:
+    """The answers of docs_read_stats."""
+    return docs_read_stats(reads, engine)[0]
 
 
 def docs_diff(docs, svs, engine=None) -> list:

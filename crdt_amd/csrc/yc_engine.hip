@@ -25,6 +25,7 @@
 #include "yc_comm.h"
 #include "yc_sync.h"
 #include "yc_json.h"
+#include "yc_read.h"
 #include "yc_store.h"
 #include <thread>
 #include <atomic>
@@ -3118,13 +3119,31 @@ struct JsonWant {            // one distinct (document, root, kind) of the devic
   bool refused = false, done = false;
 };
 
-// One device pass: the documents dl merged as one multi-document batch, the view over it, and the
-// text of the requests `ws` (indices into `wants`, their documents all in dl; pdoc maps a call
-// document to its index in dl). A request the device refuses — or every request, when the batch
-// cannot be viewed as one window or the merge fails — is left `refused` for the single path.
-int json_pass(ycrdt_engine* e, const std::vector<ycrdt_doc*>& dl, const std::vector<uint32_t>& pdoc,
-              std::vector<JsonWant>& wants, const std::vector<size_t>& ws, double& device_ms) {
-  auto refuse_all = [&]() { for (size_t k : ws) wants[k].refused = true; return YCRDT_OK; };
+// What the front half of a fleet toJSON pass leaves on the device for whatever follows it.
+struct JsonFront {
+  JsonArgs A{};
+  uint8_t* W = nullptr;      // the pass's workspace (B_JSON)
+  uint8_t* tmp = nullptr;    // scan / sort scratch
+  size_t tmpb = 0;
+  uint64_t n = 0;            // items: sorted keys + list segments
+  uint64_t o_rb = 0;         // offsets | request flags in W: read back together
+  const uint32_t* nkeys = nullptr;
+  uint8_t* xw = nullptr;     // the caller's own workspace and upload (JsonExtra), 64-byte aligned
+  uint8_t* xu = nullptr;
+  bool refused = false;      // the batch cannot be viewed as one window, or the merge failed: the single path answers
+};
+struct JsonExtra {           // what a caller other than json_pass needs beside the front half's buffers
+  uint64_t ws_fixed = 0, ws_per_item = 0, ws_per_key = 0;  // workspace bytes: fixed + per item (n + 1) + per key (ck)
+  uint64_t scan_n = 0;       // its longest scan
+  const std::vector<uint8_t>* up = nullptr;  // uploaded behind the request names
+};
+
+// The front half of one device pass, shared by ycrdt_docs_json and ycrdt_docs_read: the documents
+// dl merged as one multi-document batch, the view over it, the keys sorted into HostView::index's
+// order with the root names of `reqs` (sorted by rkey) checked, and every item sized bottom-up.
+int json_front(ycrdt_engine* e, const std::vector<ycrdt_doc*>& dl, const std::vector<JsonReq>& reqs, const std::vector<uint8_t>& names,
+               const JsonExtra& X, JsonFront& F) {
+  auto refuse_all = [&]() { F.refused = true; return YCRDT_OK; };
   const uint32_t nd = (uint32_t)dl.size();
   std::vector<Src> src;
   std::vector<uint32_t> doc_of;
@@ -3151,24 +3170,7 @@ int json_pass(ycrdt_engine* e, const std::vector<ycrdt_doc*>& dl, const std::vec
   const uint32_t nlists = e->nlists;
   const size_t ck = std::max<uint32_t>(w.cap_keys, 1);
   if ((uint64_t)ck + narr >= 0x7FFFFFF0ull) return refuse_all();
-  // the requests, sorted by (document, root name hash), and their names
-  const uint32_t nreq = (uint32_t)ws.size();
-  std::vector<size_t> order(ws);
-  std::vector<JsonReq> reqs(nreq);
-  std::vector<uint8_t> names;
-  auto rkey = [&](size_t k) {
-    return (1ull << 63) | ((uint64_t)pdoc[wants[k].doc] << 32) | (fnv_key((const uint8_t*)wants[k].name.data(), 0, (uint32_t)wants[k].name.size()) >> 1);  // as k_jsort_key hashes the root names
-  };
-  std::sort(order.begin(), order.end(), [&](size_t x, size_t y) {
-    const uint64_t a = rkey(x), c = rkey(y);
-    return a != c ? a < c : x < y;
-  });
-  for (uint32_t r = 0; r < nreq; ++r) {
-    const JsonWant& q = wants[order[r]];
-    reqs[r] = JsonReq{rkey(order[r]), (uint32_t)names.size(), (uint32_t)q.name.size(), (uint32_t)q.kind, 0};
-    names.insert(names.end(), q.name.begin(), q.name.end());
-    if (names.size() >= 0xFFFFFFF0ull) return refuse_all();
-  }
+  const uint32_t nreq = (uint32_t)reqs.size();
   // device workspace of the pass
   const uint64_t n = (uint64_t)ck + narr;
   uint64_t at = 0;
@@ -3180,18 +3182,21 @@ int json_pass(ycrdt_engine* e, const std::vector<ycrdt_doc*>& dl, const std::vec
   const uint64_t o_state = lay(4 * n), o_contrib = lay(4 * (n + 1)), o_tcontrib = lay(4ull * (narr + 1)), o_unres = lay(4 * (n + 1));
   const uint64_t o_scanc = lay(8 * (n + 1)), o_scant = lay(8ull * (narr + 1)), o_scanu = lay(4 * (n + 1));
   const uint64_t o_apos = lay(8 * n), o_cend = lay(8 * n), o_mbase = lay(8 * ck), o_abase = lay(8 * ck);
+  const uint64_t o_extra = lay(X.ws_fixed + X.ws_per_item * (n + 1) + X.ws_per_key * ck);
   const uint64_t ws_bytes = at + 64;
   at = 0;
   const uint64_t u_reqs = lay(sizeof(JsonReq) * (uint64_t)nreq), u_names = lay(names.size());
+  const uint64_t u_extra = lay(X.up ? X.up->size() : 0);
   const uint64_t up_bytes = at + 64;
   uint8_t* W = take<uint8_t>(V, B_JSON, ws_bytes, ok);
   uint8_t* U = ok ? take<uint8_t>(V, B_JSONUP, up_bytes, ok) : nullptr;
-  const size_t tmpb = prim_tmp_bytes(n + 2, ck + 2);
+  const size_t tmpb = prim_tmp_bytes(std::max<uint64_t>({n + 2, (uint64_t)nreq + 2, X.scan_n}), ck + 2);
   uint8_t* tmp = ok ? take<uint8_t>(V, B_TMP, tmpb, ok) : nullptr;
   if (!ok) return fail(YCRDT_E_DEVICE, oom("fleet toJSON"));
   std::vector<uint8_t> hup(up_bytes, 0);
   memcpy(hup.data() + u_reqs, reqs.data(), sizeof(JsonReq) * nreq);
   if (!names.empty()) memcpy(hup.data() + u_names, names.data(), names.size());
+  if (X.up && !X.up->empty()) memcpy(hup.data() + u_extra, X.up->data(), X.up->size());
   HIPCHK(hipEventRecord(e->ev0, s));
   HIPCHK(hipMemcpyAsync(U, hup.data(), up_bytes, hipMemcpyHostToDevice, s));
   HIPCHK(hipMemsetAsync(W + o_rb, 0, 8ull * (nreq + 1) + 4ull * nreq, s));
@@ -3200,7 +3205,8 @@ int json_pass(ycrdt_engine* e, const std::vector<ycrdt_doc*>& dl, const std::vec
   HIPCHK(hipMemsetAsync(W + o_abase, 0xFF, 8 * ck, s));
   HIPCHK(hipMemsetAsync(W + o_inv, 0xFF, 4 * ck, s));
   launch_view(w, vb, nsegs, nlists, narr, s);
-  JsonArgs A{};
+  JsonArgs& A = F.A;
+  A = JsonArgs{};
   A.bytes = (const uint8_t*)b.bytes.p;
   A.nbytes = b.nbytes;
   A.keys = vb.keys;
@@ -3254,6 +3260,55 @@ int json_pass(ycrdt_engine* e, const std::vector<ycrdt_doc*>& dl, const std::vec
     scan_u32(tmp, tmpb, A.unres, A.scan_u, n + 1, s);
     if (round == 0) scan_u32_to_u64(tmp, tmpb, A.tcontrib, A.scan_t, (uint64_t)narr + 1, s);
   }
+  F.W = W;
+  F.tmp = tmp;
+  F.tmpb = tmpb;
+  F.n = n;
+  F.o_rb = o_rb;
+  F.nkeys = vb.nkeys;
+  F.xw = W + o_extra;
+  F.xu = U + u_extra;
+  return YCRDT_OK;
+}
+
+// One device pass of ycrdt_docs_json: the front half over the documents dl, then the text of the
+// requests `ws` (indices into `wants`, their documents all in dl; pdoc maps a call document to its
+// index in dl). A request the device refuses — or every request, when the front half refuses the
+// batch — is left `refused` for the single path.
+int json_pass(ycrdt_engine* e, const std::vector<ycrdt_doc*>& dl, const std::vector<uint32_t>& pdoc,
+              std::vector<JsonWant>& wants, const std::vector<size_t>& ws, double& device_ms) {
+  auto refuse_all = [&]() { for (size_t k : ws) wants[k].refused = true; return YCRDT_OK; };
+  // the requests, sorted by (document, root name hash), and their names
+  const uint32_t nreq = (uint32_t)ws.size();
+  std::vector<size_t> order(ws);
+  std::vector<JsonReq> reqs(nreq);
+  std::vector<uint8_t> names;
+  auto rkey = [&](size_t k) {
+    return (1ull << 63) | ((uint64_t)pdoc[wants[k].doc] << 32) | (fnv_key((const uint8_t*)wants[k].name.data(), 0, (uint32_t)wants[k].name.size()) >> 1);  // as k_jsort_key hashes the root names
+  };
+  std::sort(order.begin(), order.end(), [&](size_t x, size_t y) {
+    const uint64_t a = rkey(x), c = rkey(y);
+    return a != c ? a < c : x < y;
+  });
+  for (uint32_t r = 0; r < nreq; ++r) {
+    const JsonWant& q = wants[order[r]];
+    reqs[r] = JsonReq{rkey(order[r]), (uint32_t)names.size(), (uint32_t)q.name.size(), (uint32_t)q.kind, 0};
+    names.insert(names.end(), q.name.begin(), q.name.end());
+    if (names.size() >= 0xFFFFFFF0ull) return refuse_all();
+  }
+  JsonFront F;
+  if (const int rc = json_front(e, dl, reqs, names, JsonExtra{}, F)) return rc;
+  if (F.refused) return refuse_all();
+  JsonArgs& A = F.A;
+  Work& w = e->w;
+  auto& V = e->bufs;
+  bool ok = true;
+  hipStream_t s = e->stream;
+  uint8_t* W = F.W;
+  uint8_t* tmp = F.tmp;
+  const size_t tmpb = F.tmpb;
+  const uint64_t o_rb = F.o_rb;
+  const size_t ck = A.ck;
   launch_json_requests(A, s);
   scan_u32_to_u64(tmp, tmpb, A.rsize, A.roffs, (uint64_t)nreq + 1, s);
   // the one size read-back: offsets (the total is the last), request flags, the view's counters
@@ -3262,7 +3317,7 @@ int json_pass(ycrdt_engine* e, const std::vector<ycrdt_doc*>& dl, const std::vec
   uint32_t nkeys = 0;
   HIPCHK(hipMemcpyAsync(rb.data(), W + o_rb, rb.size(), hipMemcpyDeviceToHost, s));
   HIPCHK(hipMemcpyAsync(&c, w.ctr, sizeof(Counters), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(&nkeys, vb.nkeys, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(&nkeys, F.nkeys, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   if (c.err || nkeys > ck) return refuse_all();
   const uint64_t* roffs = (const uint64_t*)rb.data();
@@ -3396,6 +3451,346 @@ int ycrdt_docs_json(ycrdt_engine* e, ycrdt_doc* const* docs, const char* const* 
     }
     text[i] = &it->second;
     ++S.pairs_single;
+  }
+  uint64_t total = 0;
+  for (size_t i = 0; i < n; ++i) { offs[i] = total; total += text[i]->size(); }
+  offs[n] = total;
+  uint8_t* out = (uint8_t*)malloc(total ? total : 1);
+  if (!out) return fail(YCRDT_E_CAPACITY, "host allocation failed");
+  for (size_t i = 0; i < n; ++i) memcpy(out + offs[i], text[i]->data(), text[i]->size());
+  blob->ptr = out;
+  blob->len = total;
+  S.out_bytes = total;
+  if (st) *st = S;
+  return YCRDT_OK;
+}
+
+// ---- fleet point reads (ycrdt_docs_read; yc_read.hip)
+namespace {
+
+struct ReadWant {            // one distinct read of the device path
+  uint32_t doc;              // index among the call's device documents
+  int op;
+  bool nested;
+  std::string root, pkey, key;
+  uint64_t index;
+  int32_t state = 0;
+  uint64_t count = 0;
+  std::string text;
+  bool refused = false, done = false;
+};
+
+// One device pass: the toJSON front half over the documents dl, then the reads `ws` (indices into
+// `wants`, their documents all in dl) resolved, sized and written. A read the device refuses is left
+// `refused` for the single calls.
+int read_pass(ycrdt_engine* e, const std::vector<ycrdt_doc*>& dl, const std::vector<uint32_t>& pdoc, std::vector<ReadWant>& wants,
+              const std::vector<size_t>& ws, double& device_ms) {
+  auto refuse_all = [&]() { for (size_t k : ws) wants[k].refused = true; return YCRDT_OK; };
+  const uint32_t nr = (uint32_t)ws.size();
+  // the distinct (document, root) of the reads, sorted as json_pass sorts its requests: k_jindex checks their names
+  auto rkey = [&](const ReadWant& q) {
+    return (1ull << 63) | ((uint64_t)pdoc[q.doc] << 32) | (fnv_key((const uint8_t*)q.root.data(), 0, (uint32_t)q.root.size()) >> 1);
+  };
+  std::vector<size_t> rorder(ws);
+  std::sort(rorder.begin(), rorder.end(), [&](size_t x, size_t y) {
+    const ReadWant &a = wants[x], &c = wants[y];
+    const uint64_t ka = rkey(a), kc = rkey(c);
+    return ka != kc ? ka < kc : a.root != c.root ? a.root < c.root : x < y;
+  });
+  std::vector<JsonReq> reqs;
+  std::vector<uint8_t> names;
+  std::unordered_map<size_t, uint32_t> root_of;  // want -> its root request
+  for (size_t k : rorder) {
+    const ReadWant& q = wants[k];
+    const uint64_t rk = rkey(q);
+    if (reqs.empty() || reqs.back().rkey != rk || reqs.back().name_len != q.root.size() ||
+        memcmp(names.data() + reqs.back().name_pos, q.root.data(), q.root.size()) != 0) {
+      reqs.push_back(JsonReq{rk, (uint32_t)names.size(), (uint32_t)q.root.size(), 0, 0});
+      names.insert(names.end(), q.root.begin(), q.root.end());
+    }
+    root_of[k] = (uint32_t)reqs.size() - 1;
+  }
+  std::vector<ReadReq> rr(nr);
+  for (uint32_t r = 0; r < nr; ++r) {
+    const ReadWant& q = wants[ws[r]];
+    ReadReq x{};
+    x.index = q.index;
+    x.root = root_of[ws[r]];
+    x.op = (uint32_t)q.op;
+    x.pkey_pos = (uint32_t)names.size();
+    x.pkey_len = q.nested ? (uint32_t)q.pkey.size() : READ_NONE;
+    names.insert(names.end(), q.pkey.begin(), q.pkey.end());
+    x.key_pos = (uint32_t)names.size();
+    x.key_len = (uint32_t)q.key.size();
+    names.insert(names.end(), q.key.begin(), q.key.end());
+    if (names.size() >= 0xFFFFFFF0ull) return refuse_all();
+    rr[r] = x;
+  }
+  std::vector<uint8_t> up(sizeof(ReadReq) * (size_t)nr);
+  memcpy(up.data(), rr.data(), up.size());
+  // the pass's own workspace: | offsets | counts | states | flags | (read back together) and the rest
+  uint64_t at = 0;
+  auto lay = [&](uint64_t bytes) { const uint64_t o = at; at = (at + bytes + 63) & ~uint64_t(63); return o; };
+  const uint64_t rb_bytes = 8ull * (nr + 1) + 8ull * nr + 4ull * nr + 4ull * nr;
+  const uint64_t o_rb = lay(rb_bytes);
+  const uint64_t o_voffs = o_rb, o_counts = o_voffs + 8ull * (nr + 1), o_states = o_counts + 8ull * nr, o_flags = o_states + 4ull * nr;
+  const uint64_t o_item = lay(4ull * nr), o_elem = lay(4ull * nr), o_vsize = lay(4ull * (nr + 1)), o_oflag = lay(4ull * nr);
+  const uint64_t fixed = at;
+  JsonExtra X;
+  X.ws_fixed = fixed + 4 * 64;  // (the per-key and per-item arrays below start on 64-byte lines)
+  X.ws_per_item = 12;           // vis | scan_v
+  X.ws_per_key = 8;             // own_m | own_a
+  X.scan_n = (uint64_t)nr + 2;
+  X.up = &up;
+  JsonFront F;
+  if (const int rc = json_front(e, dl, reqs, names, X, F)) return rc;
+  if (F.refused) return refuse_all();
+  JsonArgs& A = F.A;
+  auto& V = e->bufs;
+  bool ok = true;
+  hipStream_t s = e->stream;
+  const uint64_t n = F.n, ck = A.ck;
+  const uint64_t o_ownm = lay(4 * ck), o_owna = lay(4 * ck), o_vis = lay(4 * (n + 1)), o_scanv = lay(8 * (n + 1));
+  uint8_t* X0 = F.xw;
+  A.own_m = (uint32_t*)(X0 + o_ownm);
+  A.own_a = (uint32_t*)(X0 + o_owna);
+  A.oflag = (uint32_t*)(X0 + o_oflag);
+  A.nown = nr;
+  ReadArgs R{};
+  R.reads = (const ReadReq*)F.xu;
+  R.nreads = nr;
+  R.vis = (uint32_t*)(X0 + o_vis);
+  R.scan_v = (uint64_t*)(X0 + o_scanv);
+  R.item = (uint32_t*)(X0 + o_item);
+  R.elem = (uint32_t*)(X0 + o_elem);
+  R.vsize = (uint32_t*)(X0 + o_vsize);
+  R.voffs = (uint64_t*)(X0 + o_voffs);
+  R.counts = (uint64_t*)(X0 + o_counts);
+  R.states = (int32_t*)(X0 + o_states);
+  R.flags = (uint32_t*)(X0 + o_flags);
+  R.j = A;
+  HIPCHK(hipMemsetAsync(X0 + o_ownm, 0xFF, 4 * ck, s));
+  HIPCHK(hipMemsetAsync(X0 + o_owna, 0xFF, 4 * ck, s));
+  HIPCHK(hipMemsetAsync(X0 + o_oflag, 0, 4ull * nr, s));
+  launch_read_visible(R, s);
+  scan_u32_to_u64(F.tmp, F.tmpb, R.vis, R.scan_v, n + 1, s);
+  launch_read_resolve(R, s);
+  scan_u32_to_u64(F.tmp, F.tmpb, R.vsize, R.voffs, (uint64_t)nr + 1, s);
+  // the one size read-back: offsets (the total is the last), counts, states, flags, the view's counters
+  std::vector<uint8_t> rb(rb_bytes);
+  Counters c;
+  uint32_t nkeys = 0;
+  HIPCHK(hipMemcpyAsync(rb.data(), X0 + o_rb, rb.size(), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(&c, e->w.ctr, sizeof(Counters), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(&nkeys, F.nkeys, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (c.err || nkeys > ck) return refuse_all();
+  const uint64_t* voffs = (const uint64_t*)rb.data();
+  const uint64_t* counts = (const uint64_t*)(rb.data() + 8ull * (nr + 1));
+  const int32_t* states = (const int32_t*)(rb.data() + 8ull * (nr + 1) + 8ull * nr);
+  const uint32_t* flags = (const uint32_t*)(rb.data() + 8ull * (nr + 1) + 8ull * nr + 4ull * nr);
+  const uint64_t total = voffs[nr];
+  std::vector<uint8_t> text(total);
+  std::vector<uint32_t> oflag(nr, 0);
+  if (total) {
+    uint8_t* outb = take<uint8_t>(V, B_PACK, total + 64, ok);
+    if (!ok) return fail(YCRDT_E_DEVICE, oom("fleet read text"));
+    R.j.out = A.out = outb;
+    R.j.out_cap = A.out_cap = total;
+    // scalar values and the seeds of nested types, then offsets top-down and the members' bytes
+    launch_read_write(R, s);
+    for (uint32_t level = 0; level <= JSON_DEPTH_MAX; ++level) launch_json_place(A, s);
+    launch_json_write(A, s);
+    HIPCHK(hipEventRecord(e->ev1, s));
+    HIPCHK(hipMemcpyAsync(oflag.data(), A.oflag, 4ull * nr, hipMemcpyDeviceToHost, s));
+    if (const int rc2 = d2h_span(e, text.data(), outb, total)) return rc2;
+  } else {
+    HIPCHK(hipEventRecord(e->ev1, s));
+  }
+  HIPCHK(hipStreamSynchronize(s));
+  float ms = 0;
+  hipEventElapsedTime(&ms, e->ev0, e->ev1);
+  device_ms += ms;
+  for (uint32_t r = 0; r < nr; ++r) {
+    ReadWant& q = wants[ws[r]];
+    if (flags[r] || oflag[r]) { q.refused = true; continue; }
+    q.state = states[r];
+    q.count = counts[r];
+    q.text.assign((const char*)text.data() + voffs[r], voffs[r + 1] - voffs[r]);
+    q.done = true;
+  }
+  return YCRDT_OK;
+}
+
+uint64_t read_pass_bytes() {  // (tests shrink a pass through YCRDT_DOCS_READ_PASS_BYTES, as YCRDT_DOCS_JSON_PASS_BYTES does)
+  const char* v = getenv("YCRDT_DOCS_READ_PASS_BYTES");
+  const uint64_t x = v ? strtoull(v, nullptr, 10) : 0;
+  return x ? std::min(x, JSON_PASS_BYTES) : JSON_PASS_BYTES;
+}
+
+struct ReadAnswer {
+  int32_t state = 0;
+  uint64_t count = 0;
+  std::string text;
+};
+
+// read i through the single call of its op
+int read_single(const ycrdt_read& q, ReadAnswer& a) {
+  ycrdt_out o{nullptr, 0};
+  int rc = YCRDT_OK, st = 0;
+  switch (q.op) {
+    case YCRDT_READ_MAP_GET: rc = ycrdt_map_get(q.doc, q.root, q.parent_key, q.key, &st, &o); break;
+    case YCRDT_READ_ARRAY_GET: rc = ycrdt_array_get(q.doc, q.root, q.parent_key, q.index, &st, &o); break;
+    case YCRDT_READ_MAP_SIZE: {
+      uint32_t size = 0;
+      rc = ycrdt_map_size(q.doc, q.root, q.parent_key, &size);
+      a.count = size;
+      st = 1;
+      break;
+    }
+    default: rc = ycrdt_array_length(q.doc, q.root, q.parent_key, &a.count); st = 1;
+  }
+  if (rc) return rc;
+  a.state = st;
+  if (o.ptr) a.text.assign((const char*)o.ptr, o.len);
+  ycrdt_free(&o);
+  return YCRDT_OK;
+}
+
+}  // namespace
+
+int ycrdt_docs_read(ycrdt_engine* e, const ycrdt_read* reads, size_t n, ycrdt_out* blob, uint64_t* offs, int32_t* states,
+                    uint64_t* counts, ycrdt_read_stats* st) {
+  if (!e || !blob || !offs || (n && (!reads || !states || !counts))) return fail(YCRDT_E_ARG, "null arg");
+  for (size_t i = 0; i < n; ++i) {
+    const ycrdt_read& q = reads[i];
+    if (!q.doc || q.doc->e != e) return fail(YCRDT_E_ARG, "document of another engine (or null) at " + std::to_string(i));
+    if (!q.root) return fail(YCRDT_E_ARG, "null root at " + std::to_string(i));
+    if (q.op < YCRDT_READ_MAP_GET || q.op > YCRDT_READ_ARRAY_LENGTH) return fail(YCRDT_E_ARG, "op outside the four at " + std::to_string(i));
+    if (q.op == YCRDT_READ_MAP_GET && !q.key) return fail(YCRDT_E_ARG, "null key at " + std::to_string(i));
+  }
+  blob->ptr = nullptr;
+  blob->len = 0;
+  offs[0] = 0;
+  ycrdt_read_stats S{};
+  S.depth_max = JSON_DEPTH_MAX;
+  S.name_max = JSON_NAME_MAX;
+  if (st) *st = S;
+  if (n == 0) {
+    blob->ptr = (uint8_t*)malloc(1);
+    if (!blob->ptr) return fail(YCRDT_E_CAPACITY, "host allocation failed");
+    return YCRDT_OK;
+  }
+  if (n >= 0x7FFFFFFFull) return fail(YCRDT_E_CAPACITY, "too many reads");
+  HIPCHK(hipSetDevice(e->device));
+  {
+    std::vector<ycrdt_doc*> docs(n);
+    for (size_t i = 0; i < n; ++i) docs[i] = reads[i].doc;
+    if (const int rc = flush_queued(e, docs.data(), n)) return rc;
+  }
+  // which path every read takes; the device path's distinct documents and reads
+  enum : uint8_t { K_SINGLE = 0, K_EMPTY, K_DEV };
+  const bool off = env_off("YCRDT_DOCS_READ");
+  std::vector<uint8_t> kind(n, K_SINGLE);
+  std::vector<size_t> want_of(n, 0);
+  std::unordered_map<const ycrdt_doc*, uint32_t> dix;
+  std::vector<ycrdt_doc*> dlist;
+  std::vector<ReadWant> wants;
+  std::unordered_map<std::string, size_t> wix;
+  auto read_key = [](const void* who, size_t who_bytes, const ycrdt_read& q) {  // a read's identity: lengths in front of the names
+    std::string key((const char*)who, who_bytes);
+    const bool get_key = q.op == YCRDT_READ_MAP_GET;
+    const uint64_t idx = q.op == YCRDT_READ_ARRAY_GET ? q.index : 0;
+    const uint64_t lens[3] = {strlen(q.root), q.parent_key ? strlen(q.parent_key) + 1 : 0, get_key ? strlen(q.key) : 0};
+    key.push_back((char)q.op);
+    key.append((const char*)&idx, 8);
+    key.append((const char*)lens, sizeof lens);
+    key += q.root;
+    if (q.parent_key) key += q.parent_key;
+    if (get_key) key += q.key;
+    return key;
+  };
+  for (size_t i = 0; i < n; ++i) {
+    const ycrdt_read& q = reads[i];
+    ycrdt_doc* d = q.doc;
+    if (off || d->ing.has_pending || d->ing.has_ds || e->compat == 135) continue;
+    if (!d->state_len) { kind[i] = K_EMPTY; continue; }
+    if (d->state_len >= JSON_PASS_BYTES) continue;
+    if (q.parent_key && strlen(q.parent_key) > JSON_NAME_MAX) continue;
+    if (q.op == YCRDT_READ_MAP_GET && strlen(q.key) > JSON_NAME_MAX) continue;
+    kind[i] = K_DEV;
+    auto it = dix.find(d);
+    if (it == dix.end()) { it = dix.emplace(d, (uint32_t)dlist.size()).first; dlist.push_back(d); }
+    const std::string key = read_key(&it->second, 4, q);
+    auto wt = wix.find(key);
+    if (wt == wix.end()) {
+      wt = wix.emplace(key, wants.size()).first;
+      ReadWant w;
+      w.doc = it->second;
+      w.op = q.op;
+      w.nested = q.parent_key != nullptr;
+      w.root = q.root;
+      if (q.parent_key) w.pkey = q.parent_key;
+      if (q.op == YCRDT_READ_MAP_GET) w.key = q.key;
+      w.index = q.op == YCRDT_READ_ARRAY_GET ? q.index : 0;
+      wants.push_back(std::move(w));
+    }
+    want_of[i] = wt->second;
+  }
+  // device passes: documents in call order, as many as one window holds
+  if (!wants.empty()) {
+    const uint64_t pass_bytes = read_pass_bytes();
+    std::vector<std::vector<size_t>> by_doc(dlist.size());
+    for (size_t k = 0; k < wants.size(); ++k) by_doc[wants[k].doc].push_back(k);
+    std::vector<uint32_t> pdoc(dlist.size(), 0);
+    size_t j = 0;
+    while (j < dlist.size()) {
+      std::vector<ycrdt_doc*> dl;
+      std::vector<size_t> ws;
+      uint64_t bytes = 0;
+      while (j < dlist.size() && (dl.empty() || bytes + dlist[j]->state_len + 64 <= pass_bytes)) {
+        bytes += (dlist[j]->state_len + 63) & ~size_t(63);
+        pdoc[j] = (uint32_t)dl.size();
+        dl.push_back(dlist[j]);
+        ws.insert(ws.end(), by_doc[j].begin(), by_doc[j].end());
+        ++j;
+      }
+      if (const int rc = read_pass(e, dl, pdoc, wants, ws, S.device_ms)) return rc;
+    }
+  }
+  // everything else one by one (a repeated read once)
+  std::unordered_map<std::string, ReadAnswer> singles;
+  std::vector<const std::string*> text(n, nullptr);
+  static const std::string none;
+  for (size_t i = 0; i < n; ++i) {
+    const ycrdt_read& q = reads[i];
+    const bool sized = q.op == YCRDT_READ_MAP_SIZE || q.op == YCRDT_READ_ARRAY_LENGTH;
+    if (kind[i] == K_EMPTY) {
+      text[i] = &none;
+      states[i] = sized ? 1 : 0;
+      counts[i] = 0;
+      ++S.reads_empty;
+      continue;
+    }
+    if (kind[i] == K_DEV && wants[want_of[i]].done) {
+      const ReadWant& w = wants[want_of[i]];
+      text[i] = &w.text;
+      states[i] = w.state;
+      counts[i] = w.count;
+      ++S.reads_device;
+      continue;
+    }
+    const std::string key = read_key(&q.doc, sizeof q.doc, q);
+    auto it = singles.find(key);
+    if (it == singles.end()) {
+      ReadAnswer a;
+      if (const int rc = read_single(q, a)) return rc;
+      it = singles.emplace(key, std::move(a)).first;
+    }
+    text[i] = &it->second.text;
+    states[i] = it->second.state;
+    counts[i] = it->second.count;
+    ++S.reads_single;
   }
   uint64_t total = 0;
   for (size_t i = 0; i < n; ++i) { offs[i] = total; total += text[i]->size(); }

@@ -400,6 +400,11 @@ struct JsonArgs {
   uint64_t* roffs;           // [nreq + 1]
   uint8_t* out;
   uint64_t out_cap;
+  // point reads only (ycrdt_docs_read seeds many containers; nullptr: every position comes from a root)
+  uint32_t* own_m;           // [ck] group start -> the read whose value the map's text belongs to
+  uint32_t* own_a;           // [ck] list key -> ...
+  uint32_t* oflag;           // [nown] 1: the read's value holds a container another read seeded
+  uint32_t nown;
 };
 
 void launch_json_sort_key(const JsonArgs& a, uint32_t pass, const uint32_t* ord_in, uint64_t* key, hipStream_t s);
@@ -411,4 +416,109 @@ void launch_json_place(const JsonArgs& a, hipStream_t s);          // one level 
 void launch_json_write(const JsonArgs& a, hipStream_t s);
 
 }  // namespace yc
+#ifdef YC_JSON_DEVICE
+// ---- device helpers over JsonArgs, shared by the toJSON kernels (yc_json.hip) and the point-read
+// kernels (yc_read.hip)
+namespace yc {
+namespace {
+
+constexpr uint64_t NONE64 = ~0ull;
+constexpr uint64_t TEXT_BIT = 1ull << 63;
+enum : uint32_t { JS_OPEN = 0, JS_SIZED = 1, JS_REFUSED = 2 };
+enum : uint32_t { EM_OK = 0, EM_OMIT = 1, EM_PENDING = 2, EM_REFUSED = 3 };
+enum : uint32_t { BOX_MAP = 0, BOX_ARRAY = 1, BOX_TEXT = 2, BOX_XML = 3 };
+
+__device__ __forceinline__ uint64_t ld64(const uint64_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void st64(uint64_t* p, uint64_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+__device__ __forceinline__ uint32_t lower_bound_u64(const uint64_t* __restrict__ a, uint32_t n, uint64_t key) {
+  uint32_t lo = 0, hi = n;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (a[mid] < key) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+__device__ __forceinline__ uint32_t upper_bound_u64(const uint64_t* __restrict__ a, uint32_t n, uint64_t key) {
+  uint32_t lo = 0, hi = n;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (a[mid] <= key) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+__device__ __forceinline__ bool in_bytes(const JsonArgs& a, uint32_t pos, uint32_t len) { return (uint64_t)pos + len <= a.nbytes; }
+
+// the first YArray / YText list among the keys [lo, hi) of one container (lists sort in front:
+// they carry no entry name)
+__device__ __forceinline__ uint32_t first_list(const JsonArgs& a, uint32_t lo, uint32_t hi) {
+  for (uint32_t p = lo; p < hi; ++p) {
+    const uint32_t i = a.ord[p];
+    if (i >= a.ck) return VNONE;
+    const ViewKey& K = a.keys[i];
+    if (!(K.flags & VK_PSUB)) return p;
+    if (K.psub_len) return VNONE;
+  }
+  return VNONE;
+}
+
+struct Box {                 // a nested type's text
+  uint64_t size;
+  uint32_t unres;            // members not sized
+  uint32_t mode;             // BOX_*
+  uint32_t lo;               // BOX_MAP: first key of its group (VNONE: no entry); else its list key (VNONE: no list)
+};
+
+__device__ __forceinline__ uint64_t boxed(uint64_t members) { return 2 + members - (members ? 1 : 0); }  // (every member ends in a separator)
+
+// segment items [x0, x1) of list key at sorted position kp
+__device__ __forceinline__ bool list_range(const JsonArgs& a, uint32_t kp, uint32_t& x0, uint32_t& x1) {
+  const uint32_t i = a.ord[kp];
+  if (i >= a.ck) return false;
+  const ViewKey& K = a.keys[i];
+  if ((uint64_t)K.seg0 + K.nseg > a.narr) return false;
+  x0 = K.seg0;
+  x1 = K.seg0 + K.nseg;
+  return true;
+}
+
+__device__ __forceinline__ Box type_box(const JsonArgs& a, uint32_t unit, uint32_t tr) {
+  Box b{2, 0, BOX_ARRAY, VNONE};
+  if (tr >= 3 && tr <= 6) { b.mode = BOX_XML; return b; }
+  const uint32_t lo = lower_bound_u64(a.gk, a.ck, unit), hi = upper_bound_u64(a.gk, a.ck, unit);
+  if (tr == 1) {
+    b.mode = BOX_MAP;
+    if (lo < hi) {
+      b.lo = lo;
+      b.size = boxed(a.scan_c[hi] - a.scan_c[lo]);
+      b.unres = a.scan_u[hi] - a.scan_u[lo];
+    }
+    return b;
+  }
+  b.mode = tr == 2 ? BOX_TEXT : BOX_ARRAY;
+  const uint32_t kp = first_list(a, lo, hi);
+  uint32_t x0 = 0, x1 = 0;
+  if (kp == VNONE) return b;
+  if (!list_range(a, kp, x0, x1)) { b.unres = 1; return b; }
+  b.lo = kp;
+  if (tr == 2) {
+    b.size = 2 + (a.scan_t[x1] - a.scan_t[x0]);
+  } else {
+    b.size = boxed(a.scan_c[a.ck + x1] - a.scan_c[a.ck + x0]);
+    b.unres = a.scan_u[a.ck + x1] - a.scan_u[a.ck + x0];
+  }
+  return b;
+}
+
+__device__ __forceinline__ bool entry_live(const ViewKey& K) {
+  return (K.flags & VK_PSUB) && (K.win.flags & VS_SET) && !(K.win.flags & VS_DELETED) && (K.win.flags & VS_ITEM);
+}
+__device__ __forceinline__ bool member_live(const ViewSeg& s) {
+  return !(s.flags & VS_DELETED) && (s.flags & VS_COUNTABLE) && (s.flags & VS_ITEM);
+}
+
+}  // namespace
+}  // namespace yc
+#endif
 #endif

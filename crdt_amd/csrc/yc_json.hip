@@ -21,39 +21,12 @@
 // container above it unsized: the request is flagged and the host answers it through ycrdt_doc_json,
 // whose writer (yc_host.cpp) is built from the same value writer and segment cursor (yc_json.h).
 #include "yc_common.h"
+#define YC_JSON_DEVICE  // the device helpers shared with yc_read.hip
 #include "yc_json.h"
 
 namespace yc {
 
 namespace {
-
-constexpr uint64_t NONE64 = ~0ull;
-constexpr uint64_t TEXT_BIT = 1ull << 63;
-enum : uint32_t { JS_OPEN = 0, JS_SIZED = 1, JS_REFUSED = 2 };
-enum : uint32_t { EM_OK = 0, EM_OMIT = 1, EM_PENDING = 2, EM_REFUSED = 3 };
-enum : uint32_t { BOX_MAP = 0, BOX_ARRAY = 1, BOX_TEXT = 2, BOX_XML = 3 };
-
-__device__ __forceinline__ uint64_t ld64(const uint64_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st64(uint64_t* p, uint64_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__device__ __forceinline__ uint32_t lower_bound_u64(const uint64_t* __restrict__ a, uint32_t n, uint64_t key) {
-  uint32_t lo = 0, hi = n;
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (a[mid] < key) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-__device__ __forceinline__ uint32_t upper_bound_u64(const uint64_t* __restrict__ a, uint32_t n, uint64_t key) {
-  uint32_t lo = 0, hi = n;
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (a[mid] <= key) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-
-__device__ __forceinline__ bool in_bytes(const JsonArgs& a, uint32_t pos, uint32_t len) { return (uint64_t)pos + len <= a.nbytes; }
 
 // the container a view key belongs to: its parent type item's unit, or (document, root name)
 __device__ __forceinline__ uint64_t group_key(const JsonArgs& a, const ViewKey& K) {
@@ -111,67 +84,6 @@ __global__ void k_jindex(JsonArgs a) {
   }
 }
 
-// the first YArray / YText list among the keys [lo, hi) of one container (lists sort in front:
-// they carry no entry name)
-__device__ __forceinline__ uint32_t first_list(const JsonArgs& a, uint32_t lo, uint32_t hi) {
-  for (uint32_t p = lo; p < hi; ++p) {
-    const uint32_t i = a.ord[p];
-    if (i >= a.ck) return VNONE;
-    const ViewKey& K = a.keys[i];
-    if (!(K.flags & VK_PSUB)) return p;
-    if (K.psub_len) return VNONE;
-  }
-  return VNONE;
-}
-
-struct Box {                 // a nested type's text
-  uint64_t size;
-  uint32_t unres;            // members not sized
-  uint32_t mode;             // BOX_*
-  uint32_t lo;               // BOX_MAP: first key of its group (VNONE: no entry); else its list key (VNONE: no list)
-};
-
-__device__ __forceinline__ uint64_t boxed(uint64_t members) { return 2 + members - (members ? 1 : 0); }  // (every member ends in a separator)
-
-// segment items [x0, x1) of list key at sorted position kp
-__device__ __forceinline__ bool list_range(const JsonArgs& a, uint32_t kp, uint32_t& x0, uint32_t& x1) {
-  const uint32_t i = a.ord[kp];
-  if (i >= a.ck) return false;
-  const ViewKey& K = a.keys[i];
-  if ((uint64_t)K.seg0 + K.nseg > a.narr) return false;
-  x0 = K.seg0;
-  x1 = K.seg0 + K.nseg;
-  return true;
-}
-
-__device__ __forceinline__ Box type_box(const JsonArgs& a, uint32_t unit, uint32_t tr) {
-  Box b{2, 0, BOX_ARRAY, VNONE};
-  if (tr >= 3 && tr <= 6) { b.mode = BOX_XML; return b; }
-  const uint32_t lo = lower_bound_u64(a.gk, a.ck, unit), hi = upper_bound_u64(a.gk, a.ck, unit);
-  if (tr == 1) {
-    b.mode = BOX_MAP;
-    if (lo < hi) {
-      b.lo = lo;
-      b.size = boxed(a.scan_c[hi] - a.scan_c[lo]);
-      b.unres = a.scan_u[hi] - a.scan_u[lo];
-    }
-    return b;
-  }
-  b.mode = tr == 2 ? BOX_TEXT : BOX_ARRAY;
-  const uint32_t kp = first_list(a, lo, hi);
-  uint32_t x0 = 0, x1 = 0;
-  if (kp == VNONE) return b;
-  if (!list_range(a, kp, x0, x1)) { b.unres = 1; return b; }
-  b.lo = kp;
-  if (tr == 2) {
-    b.size = 2 + (a.scan_t[x1] - a.scan_t[x0]);
-  } else {
-    b.size = boxed(a.scan_c[a.ck + x1] - a.scan_c[a.ck + x0]);
-    b.unres = a.scan_u[a.ck + x1] - a.scan_u[a.ck + x0];
-  }
-  return b;
-}
-
 // The elements of a visible view segment as JSON (SegCursor, yc_json.h). `entry`: a YMap entry's
 // value — its one element, nothing behind it, EM_OMIT when it is undefined; otherwise every
 // element followed by a separator, except the one that would stand where the container closes.
@@ -208,13 +120,6 @@ __device__ __forceinline__ uint32_t emit_seg(const JsonArgs& a, const ViewSeg& s
     if (entry) return EM_OK;
     if (!o.o || o.n != cend) o.ch(',');
   }
-}
-
-__device__ __forceinline__ bool entry_live(const ViewKey& K) {
-  return (K.flags & VK_PSUB) && (K.win.flags & VS_SET) && !(K.win.flags & VS_DELETED) && (K.win.flags & VS_ITEM);
-}
-__device__ __forceinline__ bool member_live(const ViewSeg& s) {
-  return !(s.flags & VS_DELETED) && (s.flags & VS_COUNTABLE) && (s.flags & VS_ITEM);
 }
 
 // sweep 1, one level: sizes of the items still open
@@ -334,12 +239,14 @@ __global__ void k_jplace(JsonArgs a) {
   uint64_t at = NONE64, end = NONE64;
   const ViewSeg* sg = nullptr;
   uint64_t vpos = 0;
+  uint32_t owner = VNONE;  // (point reads: the read this item's container was placed for)
   if (i < a.ck) {
     if (!a.contrib[i]) return;
     const uint64_t g = a.gk[i];
     const uint32_t lo = lower_bound_u64(a.gk, a.ck, g), hi = upper_bound_u64(a.gk, a.ck, g);
     const uint64_t base = ld64(&a.mbase[lo]);
     if (base == NONE64) return;
+    if (a.own_m) { __threadfence(); owner = __hip_atomic_load(&a.own_m[lo], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
     at = base + 1 + (a.scan_c[i] - a.scan_c[lo]);
     end = base + (a.scan_c[hi] - a.scan_c[lo]);  // = base + boxed(..) - 1
     const ViewKey& K = a.keys[a.ord[i]];
@@ -353,6 +260,7 @@ __global__ void k_jplace(JsonArgs a) {
     if (kp == VNONE || kp >= a.ck) return;
     const uint64_t base = ld64(&a.abase[kp]);
     if (base == NONE64) return;
+    if (a.own_a) { __threadfence(); owner = __hip_atomic_load(&a.own_a[kp], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
     uint32_t x0 = 0, x1 = 0;
     if (!list_range(a, kp, x0, x1) || sp < x0 || sp >= x1) return;
     if (base & TEXT_BIT) {
@@ -375,6 +283,14 @@ __global__ void k_jplace(JsonArgs a) {
   if (!r.ok) return;
   const Box b = type_box(a, sg->unit + sg->len - 1, tr);
   if (b.lo == VNONE || b.mode == BOX_XML) return;
+  if (a.own_m) {  // a container another read seeded keeps that read's position: this read's text has a hole there
+    const uint32_t prev = atomicCAS((b.mode == BOX_MAP ? a.own_m : a.own_a) + b.lo, VNONE, owner);
+    if (prev != VNONE && prev != owner) {
+      if (owner < a.nown) atomicOr(&a.oflag[owner], 1u);
+      return;
+    }
+    __threadfence();
+  }
   if (b.mode == BOX_MAP) st64(&a.mbase[b.lo], vpos);
   else st64(&a.abase[b.lo], vpos | (b.mode == BOX_TEXT ? TEXT_BIT : 0));
 }

@@ -323,6 +323,26 @@ function rootsToJSON(docs, names, kinds) {
   return binding.docsJson(docs.map((d) => d._h), names, codes).map((t) => JSON.parse(t));
 }
 
+// batch entry (not in Yjs): many point reads in one device pass — getMap(root).get(key) / .size and
+// getArray(root).get(index) / .length, or the same on the type stored under root map key `parentKey`
+// — the `h[name].get(key)` / `.length` reads of crdt.js:423-430 for many documents after a fleet
+// ingest. requests: {doc, op: 'mapGet'|'mapSize'|'arrayGet'|'arrayLength', root, parentKey?, key?,
+// index?}. A get gives the parsed value (a nested type as its toJSON), undefined when absent or
+// `undefined`; a size or length a number. A doc may repeat.
+const READ_OPS = { mapGet: 0, mapSize: 1, arrayGet: 2, arrayLength: 3 };
+function readMany(requests) {
+  if (!Array.isArray(requests)) throw new TypeError('readMany(requests[])');
+  const ops = requests.map((q) => {
+    if (!q || !(q.op in READ_OPS)) throw new TypeError("readMany: op 'mapGet' | 'mapSize' | 'arrayGet' | 'arrayLength'");
+    return READ_OPS[q.op];
+  });
+  for (const q of requests) settle(q.doc);
+  const opt = (v) => (v === undefined ? null : v);
+  const got = binding.docsRead(requests.map((q) => q.doc._h), ops, requests.map((q) => q.root), requests.map((q) => opt(q.parentKey)),
+    requests.map((q) => opt(q.key)), requests.map((q) => opt(q.index)));
+  return got.map((t) => (typeof t === 'string' ? JSON.parse(t) : t));
+}
+
 function encodeStateVector(doc) {
   settle(doc);
   return binding.encodeStateVector(doc._h);
@@ -340,6 +360,7 @@ module.exports = {
   encodeStateVector,
   encodeStatesAsUpdates,
   rootsToJSON,
+  readMany,
   mergeUpdates: (updates) => binding.mergeUpdates(updates),
   diffUpdate: (update, sv) => binding.diffUpdate(update, sv),
   // batch entry (not in Yjs): [Y.diffUpdate(u, sv) for each pair] in one device pass — the sync

@@ -679,6 +679,82 @@ static napi_value js_docs_json(napi_env env, napi_callback_info info) {
   return arr;
 }
 
+/* docsRead(docs[], ops[], roots[], parentKeys[], keys[], indexes[]) → (string | undefined | number)[]
+ * (mapGet / mapSize / arrayGet / arrayLength of every request in one device pass, ycrdt_docs_read:
+ * the `h[name].get(key)` / `.length` reads of crdt.js:423-430 batched over documents; ops are
+ * YCRDT_READ_*; a get gives its JSON text or undefined, a size or length a number) */
+static napi_value js_docs_read(napi_env env, napi_callback_info info) {
+  size_t argc = 6;
+  napi_value argv[6];
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  uint32_t n = 0;
+  int shape = argc >= 6;
+  for (int j = 0; shape && j < 6; ++j) {
+    bool is = false;
+    uint32_t m = 0;
+    napi_is_array(env, argv[j], &is);
+    if (is) napi_get_array_length(env, argv[j], &m);
+    if (j == 0) n = m;
+    if (!is || m != n) shape = 0;
+  }
+  if (!shape) {
+    napi_throw_type_error(env, NULL, "docsRead(docs[], ops[], roots[], parentKeys[], keys[], indexes[]) of one length");
+    return NULL;
+  }
+  ycrdt_engine *e = engine(env);
+  if (!e) return NULL;
+  ycrdt_read *reads = (ycrdt_read *)calloc(n ? n : 1, sizeof(ycrdt_read));
+  uint64_t *offs = (uint64_t *)calloc((size_t)n + 1, sizeof(uint64_t));
+  int32_t *states = (int32_t *)calloc(n ? n : 1, sizeof(int32_t));
+  uint64_t *counts = (uint64_t *)calloc(n ? n : 1, sizeof(uint64_t));
+  int ok = reads && offs && states && counts;
+  if (!ok) napi_throw_error(env, NULL, "docsRead: out of host memory");
+  for (uint32_t i = 0; ok && i < n; ++i) {
+    napi_value v[6];
+    for (int j = 0; j < 6; ++j) napi_get_element(env, argv[j], i, &v[j]);
+    int32_t op = -1;
+    double index = 0;
+    napi_valuetype it;
+    reads[i].doc = get_doc(env, v[0]);
+    if (!reads[i].doc) { ok = 0; break; }
+    napi_typeof(env, v[5], &it);
+    if (napi_get_value_int32(env, v[1], &op) != napi_ok || !get_str(env, v[2], (char **)&reads[i].root, 0) ||
+        !get_str(env, v[3], (char **)&reads[i].parent_key, 1) || !get_str(env, v[4], (char **)&reads[i].key, 1) ||
+        (it == napi_number && napi_get_value_double(env, v[5], &index) != napi_ok) || index < 0 ||
+        (op == YCRDT_READ_MAP_GET && !reads[i].key) || (op == YCRDT_READ_ARRAY_GET && it != napi_number)) {
+      napi_throw_type_error(env, NULL, "docsRead: op 0..3, root and keys strings, index a number >= 0");
+      ok = 0;
+      break;
+    }
+    reads[i].op = op;
+    reads[i].index = (uint64_t)index;
+  }
+  ycrdt_out blob = {NULL, 0};
+  napi_value arr = NULL;
+  if (ok) {
+    int rc = ycrdt_docs_read(e, reads, n, &blob, offs, states, counts, NULL);
+    if (rc != YCRDT_OK) {
+      throw_rc(env, rc);
+    } else {
+      if (napi_create_array_with_length(env, n, &arr) != napi_ok) arr = NULL;
+      for (uint32_t i = 0; arr && i < n; ++i) {
+        napi_value s;
+        napi_status st;
+        if (reads[i].op == YCRDT_READ_MAP_SIZE || reads[i].op == YCRDT_READ_ARRAY_LENGTH) st = napi_create_double(env, (double)counts[i], &s);
+        else if (states[i] != 1) st = napi_get_undefined(env, &s);
+        else st = napi_create_string_utf8(env, (const char *)blob.ptr + offs[i], (size_t)(offs[i + 1] - offs[i]), &s);
+        if (st != napi_ok) { arr = NULL; break; }
+        napi_set_element(env, arr, i, s);
+      }
+      ycrdt_free(&blob);
+      if (!arr) napi_throw_error(env, NULL, "ycrdt: N-API call failed: docsRead result");
+    }
+  }
+  if (reads) for (uint32_t i = 0; i < n; ++i) { free((char *)reads[i].root); free((char *)reads[i].parent_key); free((char *)reads[i].key); }
+  free(reads); free(offs); free(states); free(counts);
+  return arr;
+}
+
 /* typeJson(doc, root, parentKey, kind) → toJSON of the root type (parentKey null) or of the YMap
  * (kind 0) / YArray (kind 1) stored under root[parentKey], reading that type's own list only */
 static napi_value js_type_json(napi_env env, napi_callback_info info) {
@@ -927,6 +1003,7 @@ static napi_value init(napi_env env, napi_value exports) {
       {"mapTypeAt", NULL, js_map_type_at, NULL, NULL, NULL, napi_default, NULL},
       {"docJson", NULL, js_doc_json, NULL, NULL, NULL, napi_default, NULL},
       {"docsJson", NULL, js_docs_json, NULL, NULL, NULL, napi_default, NULL},
+      {"docsRead", NULL, js_docs_read, NULL, NULL, NULL, napi_default, NULL},
       {"typeJson", NULL, js_type_json, NULL, NULL, NULL, napi_default, NULL},
       {"mapEntries", NULL, js_map_entries, NULL, NULL, NULL, napi_default, NULL},
       {"mapSet", NULL, js_map_set, NULL, NULL, NULL, napi_default, NULL},

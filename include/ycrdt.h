@@ -156,6 +156,46 @@ typedef struct {
 } ycrdt_json_stats;
 int ycrdt_docs_json(ycrdt_engine *e, ycrdt_doc *const *docs, const char *const *roots, const int *kinds,
                     size_t n, ycrdt_out *blob, uint64_t *offs, ycrdt_json_stats *st /* may be NULL */);
+/* Point reads for many documents in one device pass: the `h[name].has(key)` / `.get(key)` /
+ * `.length` reads of crdt.js:423-430 batched over documents. Read i gives exactly what the single
+ * call gives for the same arguments. MAP_GET / ARRAY_GET: states[i] is ycrdt_map_get's /
+ * ycrdt_array_get's state (0 absent, 1 present, 2 `undefined`), blob[offs[i] .. offs[i+1]) its json
+ * byte for byte (empty for states 0 and 2), counts[i] 0; a value that is a shared type is that
+ * type's toJSON. MAP_SIZE / ARRAY_LENGTH: counts[i] is ycrdt_map_size's / ycrdt_array_length's
+ * answer, states[i] 1, the blob range empty. parent_key NULL addresses the root type `root`, else
+ * the type stored in root map `root` under it (a type that does not exist, or of the other kind,
+ * reads as empty). offs holds n+1 entries; blob is released with ycrdt_free. A document may repeat,
+ * and so may a read (it is computed once). The pass is the fleet toJSON pass up to its sizing
+ * sweeps, then one lane per read: the entry found by binary search in the sorted view keys, the
+ * element in a scan of the visible lengths, the value written by the shared value writer (DESIGN.md
+ * §5.2e). Empty documents are answered inline. Documents with pending structs or a pending delete
+ * set, engines with compat 135, a key or parent_key over name_max bytes, a container holding an
+ * entry name over name_max bytes that shares its first name_max bytes with the request, and values
+ * the writer's bounds refuse (nested past depth_max, an `any` past 64 levels, malformed content)
+ * take the single call one by one (its error included); YCRDT_DOCS_READ=0 sends every read there.
+ * Queued applies are flushed first (one batched merge). reads_device + reads_single + reads_empty
+ * == n. n == 0 needs no device. A null doc or root, a null key for MAP_GET, an op outside the four
+ * or a document of another engine gives YCRDT_E_ARG and no output. */
+enum { YCRDT_READ_MAP_GET = 0, YCRDT_READ_MAP_SIZE = 1, YCRDT_READ_ARRAY_GET = 2, YCRDT_READ_ARRAY_LENGTH = 3 };
+typedef struct {
+  ycrdt_doc *doc;
+  const char *root;
+  const char *parent_key; /* NULL: the root type; else the type stored in root map `root` under it */
+  const char *key;        /* MAP_GET */
+  uint64_t index;         /* ARRAY_GET */
+  int op;                 /* YCRDT_READ_* */
+} ycrdt_read;
+typedef struct {
+  uint64_t reads_device;  /* answered on the device */
+  uint64_t reads_single;  /* went through the single call, one by one */
+  uint64_t reads_empty;   /* empty document: state 0 / count 0, no device work */
+  uint64_t out_bytes;
+  uint32_t depth_max;     /* nested-type levels the device path takes (constant) */
+  uint32_t name_max;      /* longest entry name (bytes) the device search takes (constant) */
+  double device_ms;       /* view and read kernels of the passes (the merge before them not included) */
+} ycrdt_read_stats;
+int ycrdt_docs_read(ycrdt_engine *e, const ycrdt_read *reads, size_t n, ycrdt_out *blob, uint64_t *offs,
+                    int32_t *states, uint64_t *counts, ycrdt_read_stats *st /* may be NULL */);
 /* Runs the deferred applies now (every read does this implicitly). */
 int ycrdt_doc_flush(ycrdt_doc *d);
 /* Whether Yjs would hold pending structs (store.pendingStructs) / a pending delete set
