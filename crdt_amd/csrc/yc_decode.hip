@@ -26,6 +26,7 @@
 #include <cstdlib>
 
 #include "yc_work.h"
+#include "yc_shape.h"
 
 namespace yc {
 
@@ -42,44 +43,7 @@ __device__ __forceinline__ uint32_t win4(const uint8_t* __restrict__ b, uint32_t
   const uint32_t* d = (const uint32_t*)(b + (p & ~3u));  // the batch buffer is padded past its end
   return __builtin_amdgcn_alignbyte(d[1], d[0], p & 3u);  // v_alignbyte_b32: the shift counts bytes
 }
-// ---- the register-window sizer (fast path of every struct walk)
-// The 24 bytes from the word holding a struct's start sit in six registers, loaded in one round
-// (from the lane's LDS window, or from the batch buffer); T marks the bytes that end a varuint
-// (high bit clear). A varuint's length is then a count of trailing zeros of T, and the few bytes
-// whose values matter (info byte, element counts, tags, short lengths) come out of the registers
-// through a three-level select: one round of loads per struct instead of one dependent LDS /
-// memory round trip per field. 24 bytes hold the common structs whole (a map set with a 5-byte
-// client id and a short value; a root-map item with its parent name and key).
-struct RegWin {
-  // named words, not an array: an array indexed through the select tree is turned back into a
-  // dynamically indexed (LDS-promoted) alloca by the compiler
-  uint32_t r0, r1, r2, r3, r4, r5;
-  uint32_t T;
-  __device__ __forceinline__ static uint32_t sel(uint32_t m, uint32_t a1, uint32_t a0) { return (a1 & m) | (a0 & ~m); }
-  __device__ __forceinline__ uint32_t word(uint32_t k) const {  // k < 6
-    const uint32_t m0 = 0u - (k & 1u), m1 = 0u - ((k >> 1) & 1u), m2 = 0u - ((k >> 2) & 1u);
-    const uint32_t a0 = sel(m0, r1, r0), a1 = sel(m0, r3, r2), a2 = sel(m0, r5, r4);
-    return sel(m2, a2, sel(m1, a1, a0));
-  }
-  __device__ __forceinline__ uint32_t byte(uint32_t i) const { return (word(i >> 2) >> ((i & 3u) * 8)) & 0xFFu; }
-  // length (1..5) of the varuint at byte i < 24; 0: it does not end inside the window within 5 bytes
-  __device__ __forceinline__ uint32_t vlen(uint32_t i) const {
-    const uint32_t t = T >> i;
-    const uint32_t e = t ? (uint32_t)__builtin_ctz(t) + 1u : 0u;
-    return e <= 5 ? e : 0u;
-  }
-  __device__ __forceinline__ static uint32_t nib(uint32_t x) {  // bit j = byte j of x < 0x80
-    return ((~x & 0x80808080u) * 0x204081u) >> 28;
-  }
-  __device__ __forceinline__ void mask() {
-    T = nib(r0) | nib(r1) << 4 | nib(r2) << 8 | nib(r3) << 12 | nib(r4) << 16 | nib(r5) << 20;
-  }
-  __device__ __forceinline__ void load(const uint32_t* g) {
-    r0 = g[0]; r1 = g[1]; r2 = g[2]; r3 = g[3]; r4 = g[4]; r5 = g[5];
-    mask();
-  }
-};
-constexpr uint32_t WIN_SPAN = 24;
+// (the register window RegWin: yc_shape.h)
 // one lib0 `any` value with a scalar tag at window byte q (tag already read): q moves past it;
 // false: another tag, or a length byte outside the window
 __device__ __forceinline__ bool win_scalar(const RegWin& x, uint32_t& q, uint32_t tag) {
@@ -3571,9 +3535,49 @@ __device__ __forceinline__ void struct_decode_one(const Work& w, uint32_t i, uin
   // rare, cost every struct one wave per SIMD: the kernel's registers cover the callee's)
   wave_flag(&w.ctr->any_json, ref0 == REF_JSON || ref0 == REF_EMBED || ref0 == REF_FORMAT || (v.anyf & ANY_KEYS) != 0);
 }
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_struct_decode(Work w, uint32_t nstructs) {
-  __shared__ __attribute__((aligned(16))) uint32_t win[256 * SD_STRIDE];
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+// A wavefront executes every branch any of its lanes takes, and 64 consecutive structs of an update
+// are a mix of shapes (Deleted runs, scalar / string / object values, root headers): in table order
+// each wavefront pays for the union of their parse paths. So the workgroup first sorts its 256
+// structs by shape class (yc_shape.h; a counting sort, ranks from LDS atomics) and lane t decodes
+// struct perm[t]: a wavefront then holds one class, or two neighbouring ones. Every struct still
+// writes its own columns at its own index, and the class is read by nothing else. The counters,
+// class bases and perm live in the padding words of the lanes' window slots (words SD_WIN / 4 ..),
+// which the staging never writes: no LDS beyond the windows, and no barrier between reading perm
+// and staging. (Passing the columns back through the slots to store them in table order saved
+// 1.7 GB of partial-line writes and cost 0.13 ms more than it: DESIGN.md §5.1.)
+// group = 0 (YCRDT_SD_GROUP=0): table order, the sort skipped (A/B in one process).
+constexpr uint32_t SD_LANES = 256;
+constexpr uint32_t SD_BINS = 16;  // NCLASS classes + the sentinel of the lanes past the last struct
+static_assert(NCLASS + 1 <= SD_BINS && SD_BINS <= SD_LANES, "one bin per class and one for the sentinel");
+static_assert(SD_STRIDE - SD_WIN / 4 >= 3, "three padding words per slot");
+constexpr uint32_t SD_CNT = SD_WIN / 4, SD_BASE = SD_WIN / 4 + 1, SD_PERM = SD_WIN / 4 + 2;
+__global__ __launch_bounds__(SD_LANES) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_struct_decode(Work w, uint32_t nstructs, uint32_t group) {
+  __shared__ __attribute__((aligned(16))) uint32_t win[SD_LANES * SD_STRIDE];
+  const uint32_t t = threadIdx.x, first = blockIdx.x * SD_LANES;
+  uint32_t i = first + t;
+  if (group) {  // (uniform: every lane of the workgroup reaches the barriers)
+    uint32_t cls = NCLASS;  // past the last struct: sorts last
+    if (i < nstructs) {
+      const uint32_t p0 = w.s_pos[i];
+      RegWin x;
+      x.load((const uint32_t*)(struct_bytes(w, i) + (p0 & ~3u)));  // (inside the 64 bytes the decode stages)
+      cls = shape_class(x, p0 & 3u);
+    }
+    if (t < SD_BINS) win[t * SD_STRIDE + SD_CNT] = 0;
+    __syncthreads();
+    const uint32_t r = atomicAdd(&win[cls * SD_STRIDE + SD_CNT], 1u);  // rank in its class
+    __syncthreads();
+    if (t < SD_BINS) {
+      uint32_t b = 0;
+#pragma unroll
+      for (uint32_t c = 0; c < SD_BINS; ++c) b += c < t ? win[c * SD_STRIDE + SD_CNT] : 0u;
+      win[t * SD_STRIDE + SD_BASE] = b;
+    }
+    __syncthreads();
+    win[(win[cls * SD_STRIDE + SD_BASE] + r) * SD_STRIDE + SD_PERM] = t;
+    __syncthreads();
+    i = first + win[t * SD_STRIDE + SD_PERM];
+  }
   if (i < nstructs) struct_decode_one<true>(w, i, win);
 }
 // the structs k_struct_decode deferred (their contents need the out-of-line `any` reader)
@@ -3813,7 +3817,8 @@ static bool launch_struct_clock_lb(const Work& w, uint32_t nstructs, uint32_t st
 
 void launch_struct_decode(const Work& w, uint32_t nstructs, hipStream_t s) {
   if (!nstructs) return;
-  hipLaunchKernelGGL(k_struct_decode, dim3((nstructs + 255) / 256), dim3(256), 0, s, w, nstructs);
+  const uint32_t group = env_off("YCRDT_SD_GROUP") ? 0u : 1u;  // (read per merge: A/B in one process)
+  hipLaunchKernelGGL(k_struct_decode, dim3((nstructs + SD_LANES - 1) / SD_LANES), dim3(SD_LANES), 0, s, w, nstructs, group);
   hipLaunchKernelGGL(k_struct_decode_deferred, dim3(std::min<uint32_t>(nstructs / 256 + 1, SD_DEFER_GRID)), dim3(256), 0, s, w);
 }
 void launch_struct_lenscan(const Work& w, uint32_t nstructs, hipStream_t s) {
