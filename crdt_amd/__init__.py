@@ -119,6 +119,41 @@ class _Read(ctypes.Structure):  # ycrdt_read
 READ_OPS = {"map_get": 0, "map_size": 1, "array_get": 2, "array_length": 3}
 
 
+class WriteStats(ctypes.Structure):
+    _fields_ = [
+        ("ops_device", ctypes.c_uint64),
+        ("ops_single", ctypes.c_uint64),
+        ("ops_empty", ctypes.c_uint64),
+        ("ops_noop", ctypes.c_uint64),
+        ("out_bytes", ctypes.c_uint64),
+        ("ranges_max", ctypes.c_uint32),
+        ("name_max", ctypes.c_uint32),
+        ("device_ms", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class _Write(ctypes.Structure):  # ycrdt_write
+    _fields_ = [
+        ("doc", ctypes.c_void_p),
+        ("root", ctypes.c_char_p),
+        ("parent_key", ctypes.c_char_p),
+        ("key", ctypes.c_char_p),
+        ("any", ctypes.c_char_p),
+        ("any_len", ctypes.c_size_t),
+        ("count", ctypes.c_uint32),
+        ("type_ref", ctypes.c_uint32),
+        ("index", ctypes.c_uint32),
+        ("length", ctypes.c_uint32),
+        ("op", ctypes.c_int),
+    ]
+
+
+WRITE_OPS = {"map_set": 0, "map_set_type": 1, "map_delete": 2, "array_insert": 3, "array_push": 4, "array_delete": 5}
+
+
 class JsonStats(ctypes.Structure):
     _fields_ = [
         ("pairs_device", ctypes.c_uint64),
@@ -167,7 +202,7 @@ EXPORTS = (
     "ycrdt_comm_unique_id", "ycrdt_comm_create", "ycrdt_comm_destroy", "ycrdt_batch_merge_sharded",
     "ycrdt_comm_sv_allreduce_max", "ycrdt_comm_ds_allgather", "ycrdt_comm_create_exchange", "ycrdt_route",
     "ycrdt_comm_fleet_sv_allreduce_max", "ycrdt_docs_states_packed", "ycrdt_comm_allgather", "ycrdt_device_count",
-    "ycrdt_docs_diff", "ycrdt_docs_json", "ycrdt_docs_read",
+    "ycrdt_docs_diff", "ycrdt_docs_json", "ycrdt_docs_read", "ycrdt_docs_write",
     "ycrdt_merge_updates_groups", "ycrdt_updates_state_vectors", "ycrdt_update_state_vector",
 )
 
@@ -250,6 +285,7 @@ def lib():
     L.ycrdt_docs_diff.argtypes = [vp, P(vp), P(_Buf), sz, P(_Out), P(ctypes.c_uint64), P(SyncStats)]
     L.ycrdt_docs_json.argtypes = [vp, P(vp), P(cs), P(i32), sz, P(_Out), P(ctypes.c_uint64), P(JsonStats)]
     L.ycrdt_docs_read.argtypes = [vp, P(_Read), sz, P(_Out), P(ctypes.c_uint64), P(ctypes.c_int32), P(ctypes.c_uint64), P(ReadStats)]
+    L.ycrdt_docs_write.argtypes = [vp, P(_Write), sz, P(_Out), P(ctypes.c_uint64), P(ctypes.c_int32), P(WriteStats)]
     L.ycrdt_merge_updates_groups.argtypes = [vp, P(_Buf), P(u32), sz, u32, P(_Out), P(ctypes.c_uint64), P(StoreStats)]
     L.ycrdt_updates_state_vectors.argtypes = [vp, P(_Buf), sz, P(_Out), P(ctypes.c_uint64), P(StoreStats)]
     L.ycrdt_update_state_vector.argtypes = [vp, _Buf, P(_Out)]
@@ -929,6 +965,69 @@ def docs_read_stats(reads, engine=None):
 def docs_read(reads, engine=None) -> list:
     """The answers of docs_read_stats."""
     return docs_read_stats(reads, engine)[0]
+
+
+def docs_write_stats(ops, engine=None):
+    """(updates, codes, stats) of many local ops in one device pass (ycrdt_docs_write): the `set` /
+    `del` / `push` / `insert` / `cut` of crdt.js:423-611 batched over documents. ops: tuples
+    (op, doc, root, arg, parent_key_or_None); arg mirrors the single call of the op:
+    "map_set" (key, any_bytes) | "map_set_type" (key, type_ref) | "map_delete" key |
+    "array_insert" (index, [any_bytes, ...]) | "array_push" [any_bytes, ...] |
+    "array_delete" (index, length). updates[i] is the update Doc.<op> would have enqueued (b"" where
+    it writes nothing), codes[i] what the single call returns (0, or YCRDT_E_ARG where Doc.<op>
+    raises YcrdtError of kind "ARG"). Every non-empty update is enqueued as a local transaction. A
+    document may repeat: its ops run in order. stats: ycrdt_write_stats as a dict."""
+    import numpy as np
+
+    def enc(x):
+        return None if x is None else x if isinstance(x, bytes) else x.encode()
+
+    n = len(ops)
+    arr = (_Write * max(n, 1))()
+    keep = []
+    for i, wr in enumerate(ops):
+        op, d, root, arg, pkey = (tuple(wr) + (None,))[:5]
+        if op not in WRITE_OPS:
+            raise ValueError(f"docs_write: op {op!r} ({' | '.join(WRITE_OPS)})")
+        w = arr[i]
+        w.doc, w.root, w.parent_key, w.op = d._h.value, enc(root), enc(pkey), WRITE_OPS[op]
+        anys = None
+        if op == "map_set":
+            key, value = arg
+            w.key, anys, w.count = enc(key), bytes(value), 1
+        elif op == "map_set_type":
+            key, w.type_ref = arg
+            w.key = enc(key)
+        elif op == "map_delete":
+            w.key = enc(arg)
+        elif op == "array_insert":
+            w.index, values = arg
+            anys, w.count = b"".join(bytes(x) for x in values), len(values)
+        elif op == "array_push":
+            anys, w.count = b"".join(bytes(x) for x in arg), len(arg)
+        else:
+            w.index, w.length = arg
+        if anys is not None:
+            keep.append(anys)
+            w.any, w.any_len = anys, len(anys)
+    eng = engine or (ops[0][1].engine if n else default_engine())
+    offs = np.zeros(n + 1, dtype=np.uint64)
+    codes = np.zeros(max(n, 1), dtype=np.int32)
+    out = _Out()
+    st = WriteStats()
+    _check(lib().ycrdt_docs_write(eng._h, arr, n, ctypes.byref(out), offs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+                                  codes.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), ctypes.byref(st)))
+    try:
+        o = offs.tolist()
+        blob = ctypes.string_at(out.ptr, out.len) if out.len else b""
+        return [blob[o[i]:o[i + 1]] for i in range(n)], codes.tolist()[:n], st.as_dict()
+    finally:
+        lib().ycrdt_free(ctypes.byref(out))
+
+
+def docs_write(ops, engine=None):
+    """(updates, codes) of docs_write_stats."""
+    return docs_write_stats(ops, engine)[:2]
 
 
 def docs_diff(docs, svs, engine=None) -> list:

@@ -26,6 +26,7 @@
 #include "yc_sync.h"
 #include "yc_json.h"
 #include "yc_read.h"
+#include "yc_write.h"
 #include "yc_store.h"
 #include <thread>
 #include <atomic>
@@ -271,6 +272,7 @@ struct ycrdt_doc {
   bool track_local = false;                 // ycrdt_doc_track_local: record local-op updates
   std::vector<std::vector<uint8_t>> local;  // local-op updates since the last ycrdt_doc_take_local_update
   size_t local_bytes = 0;
+  uint64_t local_seq = 0;                   // local-op updates enqueued so far (ycrdt_docs_write reads a single call's update back by it)
 };
 
 struct ycrdt_batch {
@@ -4420,6 +4422,7 @@ static uint32_t next_clock(ycrdt_doc* d) {
 // pass, like Yjs's local transact) and, when the host opted in, the incremental-delta list.
 static int apply_local(ycrdt_doc* d, const std::vector<uint8_t>& u) {
   enqueue(d, u.data(), u.size(), true);
+  ++d->local_seq;
   if (!d->track_local) return YCRDT_OK;
   d->local.push_back(u);
   d->local_bytes += u.size();
@@ -4585,6 +4588,382 @@ int ycrdt_array_delete(ycrdt_doc* d, const char* root, const char* parent_key, u
     if (rc2) return rc2;
   }
   if (rc) return fail(rc, err);
+  return YCRDT_OK;
+}
+
+// ---- fleet writes (ycrdt_docs_write; yc_write.hip)
+namespace {
+
+struct WriteWant {           // one op of the device path
+  size_t op;                 // its index in the call
+  uint32_t doc;              // index among the call's device documents
+  uint32_t clock;            // the new item's clock, handed out in advance
+  int32_t why = 0;           // WHY_*
+  std::vector<uint8_t> update;
+  bool refused = false;
+};
+
+const char* str_or_empty(const char* s) { return s ? s : ""; }
+
+// One device pass: the toJSON front half over the documents dl, the visible scan of the reads, then
+// the ops `ws` (indices into `wants`, their documents all in dl) planned, sized and written. An op
+// the device refuses is left `refused`: its document goes through the single calls.
+int write_pass(ycrdt_engine* e, const std::vector<ycrdt_doc*>& dl, const std::vector<uint32_t>& pdoc, const ycrdt_write* ops,
+               std::vector<WriteWant>& wants, const std::vector<size_t>& ws, double& device_ms) {
+  auto refuse_all = [&]() { for (size_t k : ws) wants[k].refused = true; return YCRDT_OK; };
+  const uint32_t nr = (uint32_t)ws.size();
+  // the distinct (document, root) of the ops, sorted as json_pass sorts its requests: k_jindex checks their names
+  auto rkey = [&](size_t k) {
+    const char* root = ops[wants[k].op].root;
+    return (1ull << 63) | ((uint64_t)pdoc[wants[k].doc] << 32) | (fnv_key((const uint8_t*)root, 0, (uint32_t)strlen(root)) >> 1);
+  };
+  std::vector<size_t> rorder(ws);
+  std::sort(rorder.begin(), rorder.end(), [&](size_t x, size_t y) {
+    const uint64_t ka = rkey(x), kc = rkey(y);
+    const int c = strcmp(ops[wants[x].op].root, ops[wants[y].op].root);
+    return ka != kc ? ka < kc : c != 0 ? c < 0 : x < y;
+  });
+  std::vector<JsonReq> reqs;
+  std::vector<uint8_t> names;
+  std::unordered_map<size_t, uint32_t> root_of;  // want -> its root request
+  for (size_t k : rorder) {
+    const char* root = ops[wants[k].op].root;
+    const size_t len = strlen(root);
+    const uint64_t rk = rkey(k);
+    if (reqs.empty() || reqs.back().rkey != rk || reqs.back().name_len != len ||
+        memcmp(names.data() + reqs.back().name_pos, root, len) != 0) {
+      reqs.push_back(JsonReq{rk, (uint32_t)names.size(), (uint32_t)len, 0, 0});
+      names.insert(names.end(), root, root + len);
+    }
+    root_of[k] = (uint32_t)reqs.size() - 1;
+  }
+  // the ops, their names and their values' bytes behind the root names
+  std::vector<WriteReq> wr(nr);
+  auto pool = [&](const void* p, size_t len) {
+    const uint32_t at = (uint32_t)names.size();
+    if (len) names.insert(names.end(), (const uint8_t*)p, (const uint8_t*)p + len);
+    return at;
+  };
+  for (uint32_t r = 0; r < nr; ++r) {
+    const WriteWant& w = wants[ws[r]];
+    const ycrdt_write& q = ops[w.op];
+    const bool map_op = q.op <= YCRDT_WRITE_MAP_DELETE;
+    const bool values = q.op == YCRDT_WRITE_MAP_SET || q.op == YCRDT_WRITE_ARRAY_INSERT || q.op == YCRDT_WRITE_ARRAY_PUSH;
+    if (names.size() + (q.parent_key ? strlen(q.parent_key) : 0) + (map_op ? strlen(q.key) : 0) + (values ? q.any_len : 0) >= 0xFFFFFFF0ull)
+      return refuse_all();
+    WriteReq x{};
+    x.root = root_of[ws[r]];
+    x.op = (uint32_t)q.op;
+    x.pkey_len = q.parent_key ? (uint32_t)strlen(q.parent_key) : READ_NONE;
+    x.pkey_pos = pool(q.parent_key, q.parent_key ? x.pkey_len : 0);
+    x.key_len = map_op ? (uint32_t)strlen(q.key) : 0;
+    x.key_pos = pool(q.key, x.key_len);
+    x.client = dl[pdoc[w.doc]]->client_id;
+    x.clock = w.clock;
+    x.index = q.index;
+    x.length = q.length;
+    x.lead = q.op == YCRDT_WRITE_MAP_SET ? 1u : q.op == YCRDT_WRITE_MAP_SET_TYPE ? q.type_ref : q.count;
+    x.any_len = values ? (uint32_t)q.any_len : 0;
+    x.any_pos = pool(q.any, x.any_len);
+    wr[r] = x;
+  }
+  std::vector<uint8_t> up(sizeof(WriteReq) * (size_t)nr);
+  memcpy(up.data(), wr.data(), up.size());
+  // the pass's own workspace: | offsets | reasons | flags | (read back together) and the rest
+  uint64_t at = 0;
+  auto lay = [&](uint64_t bytes) { const uint64_t o = at; at = (at + bytes + 63) & ~uint64_t(63); return o; };
+  const uint64_t rb_bytes = 8ull * (nr + 1) + 4ull * nr + 4ull * nr;
+  const uint64_t o_rb = lay(rb_bytes);
+  const uint64_t o_offs = o_rb, o_why = o_offs + 8ull * (nr + 1), o_flags = o_why + 4ull * nr;
+  const uint64_t o_size = lay(4ull * (nr + 1)), o_plan = lay(sizeof(WritePlan) * (uint64_t)nr);
+  const uint64_t fixed = at;
+  JsonExtra X;
+  X.ws_fixed = fixed + 4 * 64;  // (the per-item arrays below start on 64-byte lines)
+  X.ws_per_item = 12;           // vis | scan_v
+  X.scan_n = (uint64_t)nr + 2;
+  X.up = &up;
+  JsonFront F;
+  if (const int rc = json_front(e, dl, reqs, names, X, F)) return rc;
+  if (F.refused) return refuse_all();
+  JsonArgs& A = F.A;
+  auto& V = e->bufs;
+  bool ok = true;
+  hipStream_t s = e->stream;
+  const uint64_t n = F.n;
+  const uint64_t o_vis = lay(4 * (n + 1)), o_scanv = lay(8 * (n + 1));
+  uint8_t* X0 = F.xw;
+  ReadArgs R{};
+  R.vis = (uint32_t*)(X0 + o_vis);
+  R.scan_v = (uint64_t*)(X0 + o_scanv);
+  R.j = A;
+  WriteArgs Wa{};
+  Wa.ops = (const WriteReq*)F.xu;
+  Wa.nops = nr;
+  Wa.vis = R.vis;
+  Wa.scan_v = R.scan_v;
+  Wa.plan = (WritePlan*)(X0 + o_plan);
+  Wa.size = (uint32_t*)(X0 + o_size);
+  Wa.offs = (uint64_t*)(X0 + o_offs);
+  Wa.why = (int32_t*)(X0 + o_why);
+  Wa.flags = (uint32_t*)(X0 + o_flags);
+  Wa.j = A;
+  launch_read_visible(R, s);
+  scan_u32_to_u64(F.tmp, F.tmpb, R.vis, R.scan_v, n + 1, s);
+  launch_write_plan(Wa, s);
+  scan_u32_to_u64(F.tmp, F.tmpb, Wa.size, Wa.offs, (uint64_t)nr + 1, s);
+  // the first read-back: offsets (the total is the last), reasons, flags, the view's counters
+  std::vector<uint8_t> rb(rb_bytes);
+  Counters c;
+  uint32_t nkeys = 0;
+  HIPCHK(hipMemcpyAsync(rb.data(), X0 + o_rb, rb.size(), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(&c, e->w.ctr, sizeof(Counters), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(&nkeys, F.nkeys, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (c.err || nkeys > A.ck) return refuse_all();
+  const uint64_t* offs = (const uint64_t*)rb.data();
+  const int32_t* why = (const int32_t*)(rb.data() + 8ull * (nr + 1));
+  const uint32_t* flags = (const uint32_t*)(rb.data() + 8ull * (nr + 1) + 4ull * nr);
+  const uint64_t total = offs[nr];
+  std::vector<uint8_t> text(total);
+  if (total) {  // the second read-back: the updates
+    uint8_t* outb = take<uint8_t>(V, B_PACK, total + 64, ok);
+    if (!ok) return fail(YCRDT_E_DEVICE, oom("fleet write updates"));
+    Wa.j.out = outb;
+    Wa.j.out_cap = total;
+    launch_write_write(Wa, s);
+    HIPCHK(hipEventRecord(e->ev1, s));
+    if (const int rc2 = d2h_span(e, text.data(), outb, total)) return rc2;
+  } else {
+    HIPCHK(hipEventRecord(e->ev1, s));
+  }
+  HIPCHK(hipStreamSynchronize(s));
+  float ms = 0;
+  hipEventElapsedTime(&ms, e->ev0, e->ev1);
+  device_ms += ms;
+  for (uint32_t r = 0; r < nr; ++r) {
+    WriteWant& w = wants[ws[r]];
+    if (flags[r] || offs[r + 1] < offs[r] || offs[r + 1] > total) { w.refused = true; continue; }
+    w.why = why[r];
+    w.update.assign(text.data() + offs[r], text.data() + offs[r + 1]);
+  }
+  return YCRDT_OK;
+}
+
+uint64_t write_pass_bytes() {  // (tests shrink a pass through YCRDT_DOCS_WRITE_PASS_BYTES, as YCRDT_DOCS_READ_PASS_BYTES does)
+  const char* v = getenv("YCRDT_DOCS_WRITE_PASS_BYTES");
+  const uint64_t x = v ? strtoull(v, nullptr, 10) : 0;
+  return x ? std::min(x, JSON_PASS_BYTES) : JSON_PASS_BYTES;
+}
+
+// op q through the single call of its kind
+int write_single(const ycrdt_write& q) {
+  switch (q.op) {
+    case YCRDT_WRITE_MAP_SET: return ycrdt_map_set(q.doc, q.root, q.parent_key, q.key, q.any, q.any_len);
+    case YCRDT_WRITE_MAP_SET_TYPE: return ycrdt_map_set_type(q.doc, q.root, q.parent_key, q.key, q.type_ref);
+    case YCRDT_WRITE_MAP_DELETE: return ycrdt_map_delete(q.doc, q.root, q.parent_key, q.key);
+    case YCRDT_WRITE_ARRAY_INSERT: return ycrdt_array_insert(q.doc, q.root, q.parent_key, q.index, q.any, q.any_len, q.count);
+    case YCRDT_WRITE_ARRAY_PUSH: {  // YArray.push: an insert at the length
+      uint64_t length = 0;
+      if (const int rc = ycrdt_array_length(q.doc, q.root, q.parent_key, &length)) return rc;
+      if (length > 0xFFFFFFFFull) return fail(YCRDT_E_ARG, "Length exceeded!");
+      return ycrdt_array_insert(q.doc, q.root, q.parent_key, (uint32_t)length, q.any, q.any_len, q.count);
+    }
+    default: return ycrdt_array_delete(q.doc, q.root, q.parent_key, q.index, q.length);
+  }
+}
+
+// what the single call of op q refuses before it looks at the document: such an op takes no clock and is not sent to the device
+bool write_args_bad(const ycrdt_write& q) {
+  const bool map_op = q.op <= YCRDT_WRITE_MAP_DELETE;
+  if (map_op && !q.key) return true;
+  if (q.op == YCRDT_WRITE_MAP_SET_TYPE) return q.type_ref > 1;
+  if (q.op == YCRDT_WRITE_MAP_DELETE || q.op == YCRDT_WRITE_ARRAY_DELETE) return false;
+  if (!q.any && q.any_len) return true;
+  return !any_values_ok(q.any, q.any_len, q.op == YCRDT_WRITE_MAP_SET ? 1u : q.count);
+}
+
+// whether the ops `is` of one document may be planned against the same state: no two name one map
+// entry or one list, and none writes the root-map entry another one's parent_key names
+bool writes_independent(const ycrdt_write* ops, const std::vector<size_t>& is, const std::vector<uint8_t>& bad) {
+  auto id = [](std::initializer_list<const char*> parts) {  // lengths in front of the names (a null part apart from "")
+    std::string k;
+    for (const char* p : parts) {
+      const uint64_t len = p ? strlen(p) + 1 : 0;
+      k.append((const char*)&len, 8);
+      if (p) k += p;
+    }
+    return k;
+  };
+  std::unordered_set<std::string> entries, lists, root_entries, parents;
+  for (size_t i : is) {
+    if (bad[i]) continue;
+    const ycrdt_write& q = ops[i];
+    if (q.op <= YCRDT_WRITE_MAP_DELETE) {
+      if (!entries.insert(id({q.root, q.parent_key, q.key})).second) return false;
+      if (!q.parent_key) root_entries.insert(id({q.root, q.key}));
+    } else if (!lists.insert(id({q.root, q.parent_key})).second) {
+      return false;
+    }
+    if (q.parent_key) parents.insert(id({q.root, q.parent_key}));
+  }
+  for (const std::string& k : root_entries)
+    if (parents.count(k)) return false;
+  return true;
+}
+
+}  // namespace
+
+int ycrdt_docs_write(ycrdt_engine* e, const ycrdt_write* ops, size_t n, ycrdt_out* blob, uint64_t* offs, int32_t* codes,
+                     ycrdt_write_stats* st) {
+  if (!e || !blob || !offs || (n && (!ops || !codes))) return fail(YCRDT_E_ARG, "null arg");
+  for (size_t i = 0; i < n; ++i) {
+    const ycrdt_write& q = ops[i];
+    if (!q.doc || q.doc->e != e) return fail(YCRDT_E_ARG, "document of another engine (or null) at " + std::to_string(i));
+    if (!q.root) return fail(YCRDT_E_ARG, "null root at " + std::to_string(i));
+    if (q.op < YCRDT_WRITE_MAP_SET || q.op > YCRDT_WRITE_ARRAY_DELETE) return fail(YCRDT_E_ARG, "op outside the six at " + std::to_string(i));
+  }
+  blob->ptr = nullptr;
+  blob->len = 0;
+  offs[0] = 0;
+  ycrdt_write_stats S{};
+  S.ranges_max = WRITE_RANGES_MAX;
+  S.name_max = JSON_NAME_MAX;
+  if (st) *st = S;
+  if (n == 0) {
+    blob->ptr = (uint8_t*)malloc(1);
+    if (!blob->ptr) return fail(YCRDT_E_CAPACITY, "host allocation failed");
+    return YCRDT_OK;
+  }
+  if (n >= 0x7FFFFFFFull) return fail(YCRDT_E_CAPACITY, "too many ops");
+  HIPCHK(hipSetDevice(e->device));
+  {
+    std::vector<ycrdt_doc*> docs(n);
+    for (size_t i = 0; i < n; ++i) docs[i] = ops[i].doc;
+    if (const int rc = flush_queued(e, docs.data(), n)) return rc;
+  }
+  // the call's documents and the path each takes: all ops of one document take the same one
+  enum : uint8_t { K_SINGLE = 0, K_EMPTY, K_DEV };
+  const bool off = env_off("YCRDT_DOCS_WRITE");
+  std::vector<uint8_t> bad(n, 0);
+  for (size_t i = 0; i < n; ++i) bad[i] = write_args_bad(ops[i]) ? 1 : 0;
+  std::unordered_map<const ycrdt_doc*, uint32_t> cix;
+  std::vector<ycrdt_doc*> cdocs;
+  std::vector<std::vector<size_t>> cops;
+  std::vector<uint32_t> cdoc_of(n, 0);
+  for (size_t i = 0; i < n; ++i) {
+    auto it = cix.find(ops[i].doc);
+    if (it == cix.end()) { it = cix.emplace(ops[i].doc, (uint32_t)cdocs.size()).first; cdocs.push_back(ops[i].doc); cops.emplace_back(); }
+    cops[it->second].push_back(i);
+    cdoc_of[i] = it->second;
+  }
+  std::vector<uint8_t> kind(cdocs.size(), K_SINGLE);
+  std::vector<ycrdt_doc*> dlist;            // the device path's documents, in call order
+  std::vector<std::vector<size_t>> by_doc;  // ... and their wants
+  std::vector<WriteWant> wants;
+  std::vector<size_t> want_of(n, SIZE_MAX);
+  for (size_t c = 0; c < cdocs.size(); ++c) {
+    ycrdt_doc* d = cdocs[c];
+    if (off || d->ing.has_pending || d->ing.has_ds || e->compat == 135) continue;
+    if (!d->state_len) { kind[c] = K_EMPTY; continue; }
+    if (d->state_len >= JSON_PASS_BYTES) continue;
+    bool fits = true;
+    for (size_t i : cops[c]) {
+      if (bad[i]) continue;
+      const ycrdt_write& q = ops[i];
+      if (q.parent_key && strlen(q.parent_key) > JSON_NAME_MAX) fits = false;
+      if (q.op <= YCRDT_WRITE_MAP_DELETE && strlen(q.key) > JSON_NAME_MAX) fits = false;
+    }
+    if (!fits || (cops[c].size() > 1 && !writes_independent(ops, cops[c], bad))) continue;
+    kind[c] = K_DEV;
+    // op k of the document takes the clock next + the lengths of its earlier item ops
+    uint32_t clock = next_clock(d);
+    by_doc.emplace_back();
+    for (size_t i : cops[c]) {
+      if (bad[i]) continue;
+      const ycrdt_write& q = ops[i];
+      WriteWant w;
+      w.op = i;
+      w.doc = (uint32_t)dlist.size();
+      w.clock = clock;
+      clock += q.op <= YCRDT_WRITE_MAP_SET_TYPE ? 1u : q.op == YCRDT_WRITE_ARRAY_INSERT || q.op == YCRDT_WRITE_ARRAY_PUSH ? q.count : 0u;
+      want_of[i] = wants.size();
+      by_doc.back().push_back(wants.size());
+      wants.push_back(std::move(w));
+    }
+    dlist.push_back(d);
+  }
+  // device passes: documents in call order, as many as one window holds
+  if (!wants.empty()) {
+    const uint64_t pass_bytes = write_pass_bytes();
+    std::vector<uint32_t> pdoc(dlist.size(), 0);
+    size_t j = 0;
+    while (j < dlist.size()) {
+      std::vector<ycrdt_doc*> dl;
+      std::vector<size_t> ws;
+      uint64_t bytes = 0;
+      while (j < dlist.size() && (dl.empty() || bytes + dlist[j]->state_len + 64 <= pass_bytes)) {
+        bytes += (dlist[j]->state_len + 63) & ~size_t(63);
+        pdoc[j] = (uint32_t)dl.size();
+        dl.push_back(dlist[j]);
+        ws.insert(ws.end(), by_doc[j].begin(), by_doc[j].end());
+        ++j;
+      }
+      if (ws.empty()) continue;
+      if (const int rc = write_pass(e, dl, pdoc, ops, wants, ws, S.device_ms)) return rc;
+    }
+    // a flagged op, or a failed one that is not its document's last (the clocks behind it assumed it
+    // took its own), sends the document to the single calls
+    for (size_t c = 0, k = 0; c < cdocs.size(); ++c) {
+      if (kind[c] != K_DEV) continue;
+      const std::vector<size_t>& ws = by_doc[k++];
+      bool keep = true;
+      for (size_t x = 0; x < ws.size(); ++x)
+        if (wants[ws[x]].refused || (wants[ws[x]].why != WHY_OK && x + 1 < ws.size())) keep = false;
+      if (!keep) kind[c] = K_SINGLE;
+    }
+  }
+  // the ops in call order: a device op's update becomes a local transaction as apply_local makes one,
+  // every other op runs through its single call
+  std::vector<std::vector<uint8_t>> single(n);
+  std::vector<const std::vector<uint8_t>*> upd(n, nullptr);
+  static const std::vector<uint8_t> none;
+  for (size_t i = 0; i < n; ++i) {
+    const ycrdt_write& q = ops[i];
+    ycrdt_doc* d = q.doc;
+    const uint8_t path = kind[cdoc_of[i]];
+    upd[i] = &none;
+    codes[i] = YCRDT_OK;
+    if (path == K_DEV && !bad[i]) {
+      const WriteWant& w = wants[want_of[i]];
+      const std::string where = std::string(q.root) + "." + str_or_empty(q.parent_key);
+      if (w.why == WHY_NO_TYPE) codes[i] = fail(YCRDT_E_ARG, "no shared type at " + where);
+      else if (w.why == WHY_MISMATCH) codes[i] = fail(YCRDT_E_ARG, "type mismatch at " + where);
+      else if (w.why == WHY_LENGTH) codes[i] = fail(YCRDT_E_ARG, "Length exceeded!");
+      if (!w.update.empty()) {
+        if (const int rc = apply_local(d, w.update)) return rc;
+        upd[i] = &w.update;
+      }
+    } else {
+      const uint64_t seq = d->local_seq;
+      const int rc = write_single(q);
+      if (rc != YCRDT_OK && rc != YCRDT_E_ARG) return rc;
+      codes[i] = rc;
+      if (d->local_seq != seq && !d->queue.empty()) { single[i] = d->queue.back().bytes; upd[i] = &single[i]; }
+    }
+    if (path == K_DEV) ++S.ops_device; else if (path == K_EMPTY) ++S.ops_empty; else ++S.ops_single;
+    if (upd[i]->empty() && codes[i] == YCRDT_OK) ++S.ops_noop;
+  }
+  uint64_t total = 0;
+  for (size_t i = 0; i < n; ++i) { offs[i] = total; total += upd[i]->size(); }
+  offs[n] = total;
+  uint8_t* out = (uint8_t*)malloc(total ? total : 1);
+  if (!out) return fail(YCRDT_E_CAPACITY, "host allocation failed");
+  for (size_t i = 0; i < n; ++i)
+    if (!upd[i]->empty()) memcpy(out + offs[i], upd[i]->data(), upd[i]->size());
+  blob->ptr = out;
+  blob->len = total;
+  S.out_bytes = total;
+  if (st) *st = S;
   return YCRDT_OK;
 }
 

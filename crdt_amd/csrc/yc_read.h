@@ -115,4 +115,49 @@ void launch_read_resolve(const ReadArgs& a, hipStream_t s);   // the item of eve
 void launch_read_write(const ReadArgs& a, hipStream_t s);     // scalar values; brackets and seeds of nested types
 
 }  // namespace yc
+#ifdef YC_JSON_DEVICE
+// ---- the entry search over the sorted view keys, shared by the point-read kernels (yc_read.hip)
+// and the write kernels (yc_write.hip)
+namespace yc {
+namespace {
+
+struct KeyOrder {            // the sorted view keys as yc_read.h's searches read them (k_jsort_key's names)
+  const JsonArgs& a;
+  __device__ __forceinline__ const ViewKey* key(uint32_t p) const {
+    const uint32_t i = a.ord[p];
+    return i < *a.nkeys && i < a.ck ? &a.keys[i] : nullptr;
+  }
+  __device__ __forceinline__ bool named(const ViewKey* K) const { return K && (K->flags & VK_PSUB) && in_bytes(a, K->psub_pos, K->psub_len); }
+  __device__ __forceinline__ uint64_t group(uint32_t p) const { return a.gk[p]; }
+  __device__ __forceinline__ uint32_t len(uint32_t p) const {
+    const ViewKey* K = key(p);
+    return named(K) ? K->psub_len : 0u;
+  }
+  __device__ __forceinline__ const uint8_t* name(uint32_t p) const {
+    const ViewKey* K = key(p);
+    return named(K) ? a.bytes + K->psub_pos : a.bytes;
+  }
+};
+
+// the YMap entry `name` of container g: its sorted position (the lowest slot, as HostView::index keeps), or READ_NONE
+__device__ uint32_t find_entry(const JsonArgs& a, uint64_t g, const uint8_t* name, uint32_t len, uint32_t& flags) {
+  const KeyOrder e{a};
+  bool ambiguous = false;
+  uint32_t p = read_find_name(e, a.ck, g, name, len, ambiguous);
+  if (ambiguous) { flags |= RF_LONG; return READ_NONE; }
+  // a list key sorts as the empty name: the entry "" may stand behind it (bounded by the keys)
+  for (; p < a.ck; ++p) {
+    if (read_order_cmp(e.group(p), e.name(p), e.len(p), g, name, len) != 0) return READ_NONE;
+    const ViewKey* K = e.key(p);
+    if (!K) return READ_NONE;
+    if (!(K->flags & VK_PSUB)) continue;
+    if (!e.named(K)) { flags |= RF_OPEN; return READ_NONE; }
+    return p;
+  }
+  return READ_NONE;
+}
+
+}  // namespace
+}  // namespace yc
+#endif
 #endif

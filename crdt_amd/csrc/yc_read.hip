@@ -21,42 +21,6 @@ namespace yc {
 
 namespace {
 
-struct KeyOrder {            // the sorted view keys as yc_read.h's searches read them (k_jsort_key's names)
-  const JsonArgs& a;
-  __device__ __forceinline__ const ViewKey* key(uint32_t p) const {
-    const uint32_t i = a.ord[p];
-    return i < *a.nkeys && i < a.ck ? &a.keys[i] : nullptr;
-  }
-  __device__ __forceinline__ bool named(const ViewKey* K) const { return K && (K->flags & VK_PSUB) && in_bytes(a, K->psub_pos, K->psub_len); }
-  __device__ __forceinline__ uint64_t group(uint32_t p) const { return a.gk[p]; }
-  __device__ __forceinline__ uint32_t len(uint32_t p) const {
-    const ViewKey* K = key(p);
-    return named(K) ? K->psub_len : 0u;
-  }
-  __device__ __forceinline__ const uint8_t* name(uint32_t p) const {
-    const ViewKey* K = key(p);
-    return named(K) ? a.bytes + K->psub_pos : a.bytes;
-  }
-};
-
-// the YMap entry `name` of container g: its sorted position (the lowest slot, as HostView::index keeps), or READ_NONE
-__device__ uint32_t find_entry(const JsonArgs& a, uint64_t g, const uint8_t* name, uint32_t len, uint32_t& flags) {
-  const KeyOrder e{a};
-  bool ambiguous = false;
-  uint32_t p = read_find_name(e, a.ck, g, name, len, ambiguous);
-  if (ambiguous) { flags |= RF_LONG; return READ_NONE; }
-  // a list key sorts as the empty name: the entry "" may stand behind it (bounded by the keys)
-  for (; p < a.ck; ++p) {
-    if (read_order_cmp(e.group(p), e.name(p), e.len(p), g, name, len) != 0) return READ_NONE;
-    const ViewKey* K = e.key(p);
-    if (!K) return READ_NONE;
-    if (!(K->flags & VK_PSUB)) continue;
-    if (!e.named(K)) { flags |= RF_OPEN; return READ_NONE; }
-    return p;
-  }
-  return READ_NONE;
-}
-
 // The value a read names — element `elem` of segment s, or the one element of a YMap entry — written
 // to `o` as view_map_get / view_array_get write it: its state (0 none, 1 written, 2 undefined). A
 // nested type writes nothing here: `box` is its text.

@@ -343,6 +343,45 @@ function readMany(requests) {
   return got.map((t) => (typeof t === 'string' ? JSON.parse(t) : t));
 }
 
+// batch entry (not in Yjs): many local ops in one device pass — getMap(root).set(key, value) /
+// .set(key, new Y.Array() | new Y.Map()) / .delete(key) and getArray(root).insert(index, content) /
+// .push(content) / .delete(index, length), or the same on the type stored under root map key
+// `parentKey` — the `set` / `del` / `push` / `insert` / `cut` of crdt.js:423-611 for many documents
+// after a fleet ingest. ops: {doc, op: 'mapSet'|'mapSetType'|'mapDelete'|'arrayInsert'|'arrayPush'|
+// 'arrayDelete', root, parentKey?, key?, value? | content?, type? ('array' | 'map'), index?, length?}.
+// Gives [{update, error}] per op: the update the op wrote (empty where it wrote nothing: it is also
+// what takeLocalUpdate collects) and null, or the message of an op that failed as its single call
+// throws (the engine keeps the last failed op's own text; an earlier one reads 'invalid argument').
+// Every distinct doc is marked changed once, so its observers fire as after one transaction.
+const WRITE_OPS = { mapSet: 0, mapSetType: 1, mapDelete: 2, arrayInsert: 3, arrayPush: 4, arrayDelete: 5 };
+function writeMany(ops) {
+  if (!Array.isArray(ops)) throw new TypeError('writeMany(ops[])');
+  const num = (v, d = 0) => (v === undefined ? d : v);
+  const opt = (v) => (v === undefined ? null : v);
+  const rows = ops.map((q) => {
+    if (!q || !(q.op in WRITE_OPS)) throw new TypeError("writeMany: op 'mapSet' | 'mapSetType' | 'mapDelete' | 'arrayInsert' | 'arrayPush' | 'arrayDelete'");
+    const code = WRITE_OPS[q.op];
+    let values = null, count = 0, typeRef = 0;
+    if (code === 0) { values = encodeAny([q.value]); count = 1; }
+    if (code === 1) {
+      if (q.type !== 'array' && q.type !== 'map') throw new TypeError("writeMany: mapSetType needs type 'array' | 'map'");
+      typeRef = q.type === 'array' ? TYPE_ARRAY : TYPE_MAP;
+    }
+    if (code === 3 || code === 4) {
+      if (!Array.isArray(q.content)) throw new TypeError('writeMany: ' + q.op + ' needs content[]');
+      values = encodeAny(q.content);
+      count = q.content.length;
+    }
+    return [q.doc._h, code, q.root, opt(q.parentKey), code <= 2 ? opt(q.key) : null, values, count, typeRef, num(q.index), num(q.length, code === 5 ? 1 : 0)];
+  });
+  for (const q of ops) settle(q.doc);
+  const [updates, codes, message] = binding.docsWrite(rows);
+  for (const d of new Set(ops.map((q) => q.doc))) if (!d._txn) markChanged(d, true);
+  let lastFailed = -1;
+  codes.forEach((c, i) => { if (c !== 0) lastFailed = i; });
+  return updates.map((update, i) => ({ update, error: codes[i] === 0 ? null : i === lastFailed ? message : 'invalid argument' }));
+}
+
 function encodeStateVector(doc) {
   settle(doc);
   return binding.encodeStateVector(doc._h);
@@ -361,6 +400,7 @@ module.exports = {
   encodeStatesAsUpdates,
   rootsToJSON,
   readMany,
+  writeMany,
   mergeUpdates: (updates) => binding.mergeUpdates(updates),
   diffUpdate: (update, sv) => binding.diffUpdate(update, sv),
   // batch entry (not in Yjs): [Y.diffUpdate(u, sv) for each pair] in one device pass — the sync

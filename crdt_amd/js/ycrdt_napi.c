@@ -755,6 +755,104 @@ static napi_value js_docs_read(napi_env env, napi_callback_info info) {
   return arr;
 }
 
+/* docsWrite(ops[]) → [updates: Uint8Array[], codes: number[], message: string]
+ * (mapSet / mapSetType / mapDelete / arrayInsert / arrayPush / arrayDelete of every op in one device
+ * pass, ycrdt_docs_write: the `set` / `del` / `push` / `insert` / `cut` of crdt.js:423-611 batched
+ * over documents). An op is [doc, op (YCRDT_WRITE_*), root, parentKey | null, key | null,
+ * values (encoded `any`s) | null, count, typeRef, index, length]. updates[i] is the update the op
+ * enqueued (empty where it wrote nothing), codes[i] what its single call returns, message the last
+ * failed op's text. */
+static napi_value js_docs_write(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1];
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  bool is = false;
+  uint32_t n = 0;
+  if (argc >= 1) napi_is_array(env, argv[0], &is);
+  if (!is) {
+    napi_throw_type_error(env, NULL, "docsWrite(ops[])");
+    return NULL;
+  }
+  napi_get_array_length(env, argv[0], &n);
+  ycrdt_engine *e = engine(env);
+  if (!e) return NULL;
+  ycrdt_write *ops = (ycrdt_write *)calloc(n ? n : 1, sizeof(ycrdt_write));
+  uint64_t *offs = (uint64_t *)calloc((size_t)n + 1, sizeof(uint64_t));
+  int32_t *codes = (int32_t *)calloc(n ? n : 1, sizeof(int32_t));
+  int ok = ops && offs && codes;
+  if (!ok) napi_throw_error(env, NULL, "docsWrite: out of host memory");
+  for (uint32_t i = 0; ok && i < n; ++i) {
+    napi_value op, v[10];
+    bool arr = false;
+    uint32_t m = 0;
+    napi_get_element(env, argv[0], i, &op);
+    napi_is_array(env, op, &arr);
+    if (arr) napi_get_array_length(env, op, &m);
+    if (m != 10) { napi_throw_type_error(env, NULL, "docsWrite: an op is an array of 10"); ok = 0; break; }
+    for (int j = 0; j < 10; ++j) napi_get_element(env, op, j, &v[j]);
+    ops[i].doc = get_doc(env, v[0]);
+    if (!ops[i].doc) { ok = 0; break; }
+    int32_t code = -1;
+    uint32_t num[4] = {0, 0, 0, 0};
+    napi_valuetype vt;
+    ycrdt_buf any = {NULL, 0};
+    napi_typeof(env, v[5], &vt);
+    int good = napi_get_value_int32(env, v[1], &code) == napi_ok && get_str(env, v[2], (char **)&ops[i].root, 0) &&
+               get_str(env, v[3], (char **)&ops[i].parent_key, 1) && get_str(env, v[4], (char **)&ops[i].key, 1) &&
+               (vt == napi_null || vt == napi_undefined || get_bytes(env, v[5], &any));
+    for (int j = 0; good && j < 4; ++j) good = napi_get_value_uint32(env, v[6 + j], &num[j]) == napi_ok;
+    if (!good) {
+      napi_throw_type_error(env, NULL, "docsWrite: op 0..5, root and keys strings, values a Uint8Array, count, typeRef, index and length numbers");
+      ok = 0;
+      break;
+    }
+    ops[i].op = code;
+    ops[i].any = any.ptr; /* borrowed: the JS array keeps the values alive over the call */
+    ops[i].any_len = any.len;
+    ops[i].count = num[0];
+    ops[i].type_ref = num[1];
+    ops[i].index = num[2];
+    ops[i].length = num[3];
+  }
+  ycrdt_out blob = {NULL, 0};
+  napi_value res = NULL;
+  if (ok) {
+    int rc = ycrdt_docs_write(e, ops, n, &blob, offs, codes, NULL);
+    if (rc != YCRDT_OK) {
+      throw_rc(env, rc);
+    } else {
+      napi_value ups = NULL, cs = NULL, msg = NULL;
+      const char *m = ycrdt_last_error();
+      int made = napi_create_array_with_length(env, 3, &res) == napi_ok && napi_create_array_with_length(env, n, &ups) == napi_ok &&
+                 napi_create_array_with_length(env, n, &cs) == napi_ok &&
+                 napi_create_string_utf8(env, m ? m : "", NAPI_AUTO_LENGTH, &msg) == napi_ok;
+      for (uint32_t i = 0; made && i < n; ++i) {
+        napi_value ab, ta, c;
+        void *data = NULL;
+        const size_t len = (size_t)(offs[i + 1] - offs[i]);
+        made = napi_create_arraybuffer(env, len, &data, &ab) == napi_ok && napi_create_typedarray(env, napi_uint8_array, len, ab, 0, &ta) == napi_ok &&
+               napi_create_int32(env, codes[i], &c) == napi_ok;
+        if (!made) break;
+        if (len) memcpy(data, blob.ptr + offs[i], len);
+        napi_set_element(env, ups, i, ta);
+        napi_set_element(env, cs, i, c);
+      }
+      ycrdt_free(&blob);
+      if (made) {
+        napi_set_element(env, res, 0, ups);
+        napi_set_element(env, res, 1, cs);
+        napi_set_element(env, res, 2, msg);
+      } else {
+        res = NULL;
+        napi_throw_error(env, NULL, "ycrdt: N-API call failed: docsWrite result");
+      }
+    }
+  }
+  if (ops) for (uint32_t i = 0; i < n; ++i) { free((char *)ops[i].root); free((char *)ops[i].parent_key); free((char *)ops[i].key); }
+  free(ops); free(offs); free(codes);
+  return res;
+}
+
 /* typeJson(doc, root, parentKey, kind) → toJSON of the root type (parentKey null) or of the YMap
  * (kind 0) / YArray (kind 1) stored under root[parentKey], reading that type's own list only */
 static napi_value js_type_json(napi_env env, napi_callback_info info) {
@@ -1004,6 +1102,7 @@ static napi_value init(napi_env env, napi_value exports) {
       {"docJson", NULL, js_doc_json, NULL, NULL, NULL, napi_default, NULL},
       {"docsJson", NULL, js_docs_json, NULL, NULL, NULL, napi_default, NULL},
       {"docsRead", NULL, js_docs_read, NULL, NULL, NULL, napi_default, NULL},
+      {"docsWrite", NULL, js_docs_write, NULL, NULL, NULL, napi_default, NULL},
       {"typeJson", NULL, js_type_json, NULL, NULL, NULL, napi_default, NULL},
       {"mapEntries", NULL, js_map_entries, NULL, NULL, NULL, napi_default, NULL},
       {"mapSet", NULL, js_map_set, NULL, NULL, NULL, napi_default, NULL},

@@ -196,6 +196,60 @@ typedef struct {
 } ycrdt_read_stats;
 int ycrdt_docs_read(ycrdt_engine *e, const ycrdt_read *reads, size_t n, ycrdt_out *blob, uint64_t *offs,
                     int32_t *states, uint64_t *counts, ycrdt_read_stats *st /* may be NULL */);
+/* Local ops for many documents in one device pass: the `set` / `del` / `push` / `insert` / `cut` of
+ * crdt.js:423-611 batched over documents. Op i gives exactly what the single call of its kind gives
+ * for the same arguments: blob[offs[i] .. offs[i+1]) is the update that call would have enqueued,
+ * byte for byte — empty where it writes nothing: a delete of an absent or deleted entry, count == 0,
+ * length == 0, a failed op that deleted nothing — and codes[i] is what it would have returned.
+ * YCRDT_E_ARG stands for "Length exceeded!", "no shared type at ...", a type mismatch, a null key or
+ * a bad `any` value; an ARRAY_DELETE that runs past the end deletes what exists (a non-empty update)
+ * and has code YCRDT_E_ARG, as ycrdt_array_delete. ARRAY_PUSH is ARRAY_INSERT at the list's visible
+ * length (YArray.push without a read of the length first). Every non-empty update is enqueued as a
+ * local transaction, as the single calls enqueue theirs (ycrdt_doc_take_local_update sees it). The
+ * last failed op leaves its message in ycrdt_last_error. offs holds n+1 entries; blob is released
+ * with ycrdt_free. A document may repeat: its ops run in the call's order.
+ * The pass is the fleet read pass up to its visible-length scan, then one lane per op: the entry by
+ * binary search in the sorted view keys, the element at index - 1 in the scan of the visible
+ * lengths, the bytes by the writers of yc_write.h. The path is chosen per
+ * document. Empty documents run the single calls (ops_empty). The single calls, in order, also run
+ * (ops_single) the ops of documents with pending structs or a pending delete set, of engines with
+ * compat 135, with a key or parent_key over name_max bytes, whose ops in this call are not
+ * independent of one another (two name one map entry or one list, or one writes the root-map entry
+ * another's parent_key names), with an op the device flags (the reads' refusals; an ARRAY_DELETE
+ * over more than ranges_max visible segments), or with a failed op that is not the document's last;
+ * YCRDT_DOCS_WRITE=0 sends every op there (under it, and under compat 135, an empty document's ops
+ * count as ops_single too). ops_device + ops_single + ops_empty == n; ops_noop counts
+ * the ops with code 0 and an empty update. Queued applies are flushed first (one batched merge).
+ * n == 0 needs no device. The call itself fails only with YCRDT_E_ARG for a null pointer, a null
+ * doc or root, an op outside the six or a document of another engine — checked before anything is
+ * enqueued — and with what is no per-op result (YCRDT_E_DEVICE). */
+enum { YCRDT_WRITE_MAP_SET = 0, YCRDT_WRITE_MAP_SET_TYPE = 1, YCRDT_WRITE_MAP_DELETE = 2,
+       YCRDT_WRITE_ARRAY_INSERT = 3, YCRDT_WRITE_ARRAY_PUSH = 4, YCRDT_WRITE_ARRAY_DELETE = 5 };
+typedef struct {
+  ycrdt_doc *doc;
+  const char *root;
+  const char *parent_key; /* NULL: the root type; else the type stored in root map `root` under it */
+  const char *key;        /* the map ops */
+  const uint8_t *any;     /* MAP_SET: one value; ARRAY_INSERT / ARRAY_PUSH: count values */
+  size_t any_len;
+  uint32_t count;
+  uint32_t type_ref;      /* MAP_SET_TYPE: 0 = YArray, 1 = YMap */
+  uint32_t index;         /* ARRAY_INSERT, ARRAY_DELETE */
+  uint32_t length;        /* ARRAY_DELETE */
+  int op;                 /* YCRDT_WRITE_* */
+} ycrdt_write;
+typedef struct {
+  uint64_t ops_device;    /* encoded on the device */
+  uint64_t ops_single;    /* went through the single calls, in order */
+  uint64_t ops_empty;     /* empty document: the single calls, no device work */
+  uint64_t ops_noop;      /* code 0 and an empty update (whatever the path) */
+  uint64_t out_bytes;
+  uint32_t ranges_max;    /* visible segments one ARRAY_DELETE may touch on the device (constant) */
+  uint32_t name_max;      /* longest key / parent_key (bytes) the device search takes (constant) */
+  double device_ms;       /* view, sort, sizing and write kernels of the passes (the merge before them not included) */
+} ycrdt_write_stats;
+int ycrdt_docs_write(ycrdt_engine *e, const ycrdt_write *ops, size_t n, ycrdt_out *blob, uint64_t *offs /* n + 1 */,
+                     int32_t *codes /* n */, ycrdt_write_stats *st /* may be NULL */);
 /* Runs the deferred applies now (every read does this implicitly). */
 int ycrdt_doc_flush(ycrdt_doc *d);
 /* Whether Yjs would hold pending structs (store.pendingStructs) / a pending delete set
