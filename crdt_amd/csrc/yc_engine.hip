@@ -1403,7 +1403,7 @@ int run_merge(ycrdt_engine* e, ycrdt_batch* b, const std::unordered_map<uint32_t
   w.g_flags = take<uint32_t>(V, B_GFLAGS, U + 1, ok);
   w.g_origin = take<uint32_t>(V, B_GORIG, U + 1, ok);
   w.g_rorigin = take<uint32_t>(V, B_GRORIG, U + 1, ok);
-  w.g_hop = take<uint4>(V, B_GLINK, U + 1, ok);
+  w.g_hop = take<unsigned long long>(V, B_GLINK, U + 1, ok);  // 8 B per segment
   w.g_key = take<uint32_t>(V, B_GKEY, U + 1, ok);
   w.g_maxchild = take<uint32_t>(V, B_GMAXC, U + 1, ok);
   w.g_outid = take<uint32_t>(V, B_GOUTID, U + 2, ok);

@@ -458,14 +458,16 @@ __device__ __forceinline__ bool same_list(const Work& w, uint32_t a, uint32_t b)
 // with the same low hash reads the claimer from the same word and compares the two lists' names
 // exactly (same_list): equal hashes of different lists keep probing (no hash-only identity).
 // Every struct of one list walks the same probe sequence, so the list gets exactly one slot.
-__device__ __forceinline__ uint32_t key_insert(const Work& w, uint64_t h, uint32_t own) {
+// claimed: this struct's CAS took the slot — exactly one root per list sees it (the CAS decides).
+__device__ __forceinline__ uint32_t key_insert(const Work& w, uint64_t h, uint32_t own, bool& claimed) {
   uint64_t* __restrict__ tab = w.k_hash;
   const uint32_t cap = w.cap_keys;
   const uint64_t mine = ((uint64_t)(own + 1) << 32) | (uint32_t)h;
   uint32_t slot = (uint32_t)(h ^ (h >> 29)) & (cap - 1);
+  claimed = false;
   for (uint32_t probe = 0; probe < cap; ++probe) {
     const unsigned long long old = atomicCAS((unsigned long long*)&tab[slot], 0ull, (unsigned long long)mine);
-    if (old == 0ull || old == mine) return slot;
+    if (old == 0ull || old == mine) { claimed = true; return slot; }
     if ((uint32_t)old == (uint32_t)h && same_list(w, (uint32_t)(old >> 32) - 1u, own)) return slot;
     slot = (slot + 1) & (cap - 1);
   }
@@ -531,13 +533,20 @@ __device__ __forceinline__ void seg_props_at(const Work& w, uint32_t s) {
       const uint32_t ps = w.s_psub[own];
       if (ps != NONE) { h = fnv_u32(h, 0x5Au); h = fnv_bytes(h, struct_bytes(w, own) + ps, w.s_psublen[own]); }
       h &= w.key_mask;  // tests: YCRDT_KEY_HASH_BITS truncates the hash so distinct lists collide
-      key = key_insert(w, h, own);
+      bool claimed;
+      key = key_insert(w, h, own, claimed);
       if (key != NONE) YC_BOUND(w, key, w.cap_keys, BOUNDS_KEY);
       if (key == NONE) raise_err(&w.ctr->err, ERR_CAPACITY);
       else {
         sf |= SEG_ROOT;
-        w.k_parent[key] = parent;  // every root of a list names the same parent
-        if (ps != NONE) atomicOr(&w.k_flags[key], KF_PSUB);
+        // every root of a list names the same parent and the same parentSub (same_list), so the one
+        // root whose CAS claimed the slot writes both, and only what the fill (k_parent = NONE,
+        // k_flags = 0) does not already hold: no scattered store per root of a root-type list, and
+        // k_flags has no other writer before k_resolve, so its store is a plain one
+        if (claimed) {
+          if (parent != NONE) w.k_parent[key] = parent;
+          if (ps != NONE) w.k_flags[key] = KF_PSUB;
+        }
       }
     }
   } else if (!gc) {
@@ -566,11 +575,16 @@ __device__ __forceinline__ void seg_props_at(const Work& w, uint32_t s) {
   w.g_src[s] = own;
   w.g_origin[s] = gc ? NONE : origin;
   w.g_rorigin[s] = gc ? NONE : rorigin;
-  // the climbing record (k_resolve writes the final flags and keys): a root's key carries its list
-  // kind in bit 31 (k_resolve copies it whole down the chains and writes the final keys, without
-  // the bit, to g_key); the origin's segment is the winner slot of a YMap entry
-  const uint32_t kw = key != NONE && w.s_psub[own] != NONE ? key | KEY_PSUB : key;
-  w.g_hop[s] = make_uint4(sf, kw, link, !gc && origin != NONE ? link : NONE);
+  // the climbing record (yc_work.h; k_resolve writes the final flags and keys): a root's key carries
+  // its list kind in bit 31 (k_resolve copies it whole down the chains and writes the final keys,
+  // without the bit, to g_key); every other item holds its link, which is the winner slot of a YMap
+  // entry when it came from the origin (HOP_ORIGIN); a root without a key keeps link = s (k_resolve
+  // reports the chain without a root); GC holds nothing. No reader in this kernel: a plain store.
+  uint32_t hv = link;
+  if (gc) hv = NONE;
+  else if (key != NONE) { sf |= HOP_KEY; hv = w.s_psub[own] != NONE ? key | KEY_PSUB : key; }
+  else if (origin != NONE) sf |= HOP_ORIGIN;
+  w.g_hop[s] = hop_pack(sf, hv);
 }
 __global__ __launch_bounds__(256) void k_seg_props(Work w, uint32_t nsegs) {
   const uint32_t s = gidx();
@@ -592,37 +606,62 @@ void launch_segment_props(const Work& w, uint32_t nsegs, uint32_t nclients, uint
 // One pass (Item.getMissing, Y@76507): every item that is not a list root climbs its origin chain
 // to the first segment that knows its list, halving the path it walks (link[x] <- link[link[x]] is
 // monotone: it only ever points further up the same chain, so concurrent halving is safe). The
-// climb reads the keys of k_seg_props (g_tmp, with the list kind in bit 31); a resolved item
-// publishes its key there for later climbers and writes its final key (bit cleared) to g_key, so
-// no climber ever reads a key whose kind bit is gone. The item is then tagged YMap entry
-// (parentSub) or YArray member, and a YMap entry settles its origin's max-client child slot (the
-// second pass of the winner reduction begun in k_seg_props: an atomicMax only where the slot is
-// below itself — segments are numbered in client order, so the max child is the max segment).
+// climb reads the hop records of k_seg_props (g_hop: a key with the list kind in bit 31, or a link);
+// a resolved item publishes its key there for later climbers and writes its final key (bit cleared)
+// to g_key, so no climber ever reads a key whose kind bit is gone. The item is then tagged YMap
+// entry (parentSub) or YArray member, and a YMap entry settles its origin's max-client child slot
+// (the second pass of the winner reduction begun in k_seg_props: an atomicMax only where the slot
+// is below itself — segments are numbered in client order, so the max child is the max segment).
+//
+// The records are read and written by many threads of the launch at once. Why that is safe:
+//  - Every access is one 64-bit access (hop_ld / hop_st), and every writer stores a whole record
+//    that is consistent in itself: {item, link further up the same chain}, {item | HOP_KEY, the
+//    chain's key} or {GC, NONE}. A reader can therefore see an old record, never HOP_KEY beside a
+//    link or a link beside GC flags, and never indexes g_hop with anything but a link.
+//  - Three stores exist. The owner publishes its key or its GC conversion into its own record;
+//    a climber standing on x halves the path, {fx as loaded without HOP_ORIGIN, z}, where z is the
+//    link it read from x's link y while y was an item without a key: z lies further up x's chain.
+//  - A halving store may land after the owner's publication (the climber loaded x before it) and
+//    revert the record to "item, linked to z". That loses a shortcut, not an answer: a later
+//    climber walks on from z and reaches the same key, or the same GC end, since every record
+//    between x and the chain's end still says what the chain says.
+//  - Halving may also hit x's record BEFORE x's own thread has loaded it. The thread then starts
+//    its climb at z (same result), but the value is no longer its origin's segment: that is what
+//    HOP_ORIGIN tells. Halving clears it, and an entry item that finds it cleared takes its
+//    winner slot from g_origin[s], which only k_seg_props and the owner write.
+//  - The owner writes its final g_flags, g_key, g_origin and g_rorigin from registers, never from
+//    the record, so nothing another thread stores over the record reaches the result.
+//  - A stale L1 copy of a record is one of its earlier states, i.e. a not-yet-shortened or
+//    not-yet-published one: more hops, same end. The it <= nsegs bound holds as before: links only
+//    move up the chain, so a walk over an acyclic chain visits a segment at most once.
 __device__ __forceinline__ bool resolve_at(const Work& w, uint32_t s, uint32_t nsegs) {
-  const uint4 h = w.g_hop[s];  // flags, climbing key, link, origin segment
-  uint32_t f = h.x;
-  uint32_t kv = h.y;
+  const unsigned long long h = hop_ld(&w.g_hop[s]);
+  uint32_t f = (uint32_t)h;                   // flags
+  const uint32_t hv = (uint32_t)(h >> 32);    // key (HOP_KEY) or link
+  uint32_t kv = (f & HOP_KEY) ? hv : NONE;
   bool arr = false;
   if (f & SEG_ITEM) {
-    if (kv == NONE) {  // not a root: climb
-      uint32_t x = h.z;
+    if (!(f & HOP_KEY)) {  // not a root: climb
+      uint32_t x = hv;
+      unsigned long long hx = hop_ld(&w.g_hop[x]);  // one 8-B load per hop: y's record is carried over
       bool done = false;
       for (uint32_t it = 0; it <= nsegs; ++it) {  // more hops than segments: a cycle
-        const uint4 hx = w.g_hop[x];  // one 16-B load per hop
-        const uint32_t fx = hx.x, k = hx.y, y = hx.z;
+        const uint32_t fx = (uint32_t)hx, y = (uint32_t)(hx >> 32);
         if (!(fx & SEG_ITEM)) {  // the origin chain ends in GC: getMissing drops the parent
           f = (f & ~SEG_ITEM) | SEG_GC | SEG_DEL;
-          w.g_hop[s].x = f;
+          hop_st(&w.g_hop[s], f & ~HOP_ORIGIN, NONE);
           w.g_origin[s] = NONE;
           w.g_rorigin[s] = NONE;
           done = true;
           break;
         }
-        if (k != NONE) { kv = k; w.g_hop[s].y = k; done = true; break; }
+        if (fx & HOP_KEY) { kv = y; hop_st(&w.g_hop[s], (f & ~HOP_ORIGIN) | HOP_KEY, kv); done = true; break; }
         if (y == x) { done = true; break; }  // a chain without a root: reported below
-        const uint32_t z = w.g_hop[y].z;
-        if (z != y) w.g_hop[x].z = z;
+        const unsigned long long hy = hop_ld(&w.g_hop[y]);
+        const uint32_t fy = (uint32_t)hy, z = (uint32_t)(hy >> 32);
+        if ((fy & (SEG_ITEM | HOP_KEY)) == SEG_ITEM && z != y) hop_st(&w.g_hop[x], fx & ~HOP_ORIGIN, z);
         x = y;
+        hx = hy;
       }
       if (!done) raise_err(&w.ctr->err, ERR_DECODE);  // an origin cycle
     }
@@ -636,13 +675,21 @@ __device__ __forceinline__ bool resolve_at(const Work& w, uint32_t s, uint32_t n
         // YATA kernels (launch_mapx_flip / launch_mapx_fix)
         if (!arr && (f & SEG_HASRO)) { atomicOr(&w.k_flags[kv & ~KEY_PSUB], KF_YATA); w.ctr->nmapx = 1u; }
         if (!arr) {  // the winner reduction's settling pass (k_seg_props stored one child)
-          uint32_t* slot = h.w != NONE ? &w.g_maxchild[h.w] : (f & SEG_ROOT) ? &w.k_rootmax[kv & ~KEY_PSUB] : nullptr;
+          // the slot is the origin segment's: the link as k_seg_props wrote it (HOP_ORIGIN), or, when
+          // a climber halved this record before it was loaded here, the segment of g_origin[s]
+          uint32_t* slot = nullptr;
+          if (f & HOP_ORIGIN) slot = &w.g_maxchild[hv];
+          else if (f & SEG_ROOT) slot = &w.k_rootmax[kv & ~KEY_PSUB];
+          else {
+            const uint32_t o = w.g_origin[s];
+            if (o != NONE) slot = &w.g_maxchild[seg_of_unit(w, o)];
+          }
           if (slot && *slot < s + 1) atomicMax(slot, s + 1);
         }
       }
     }
   }
-  w.g_flags[s] = f & ~SEG_HASRO;
+  w.g_flags[s] = f & ~HOP_ONLY;
   w.g_key[s] = (f & SEG_ITEM) && kv != NONE ? kv & ~KEY_PSUB : NONE;
   return arr;
 }

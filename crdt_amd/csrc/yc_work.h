@@ -241,8 +241,10 @@ struct Work {
   uint32_t* g_flags = nullptr;     // SEG_* flags
   uint32_t* g_origin = nullptr;    // origin unit (global) or NONE
   uint32_t* g_rorigin = nullptr;   // right-origin unit or NONE
-  uint4* g_hop = nullptr;          // key resolution record {flags, climbing key, link, origin segment}:
-                                   // one 16-B line per climbing hop (k_seg_props -> k_resolve)
+  unsigned long long* g_hop = nullptr;  // key resolution record, one aligned 8 B per segment: flags in the low
+                                   // word (SEG_* | HOP_*), in the high word the list key (HOP_KEY) or the
+                                   // link up the origin chain: one 8-B load per climbing hop, always read
+                                   // and written whole (hop_ld / hop_st; k_seg_props -> k_resolve)
   uint32_t* g_key = nullptr;       // resolved key slot or NONE
   uint32_t* g_maxchild = nullptr;  // seg + 1 of the max-client child (segments are in client order), 0 = none
   uint32_t* g_next = nullptr;      // descent pointer / pointer jumping
@@ -698,10 +700,29 @@ enum : uint32_t {
   SEG_YMAPX = 1024u,   // a YMap entry ordered by full YATA (its key has an entry item with a right
                        // origin: the max-client descent does not apply): adjacency from g_right
   SEG_HASRO = 2048u,   // (hop record only, k_seg_props -> k_resolve) the item has a right origin
+  HOP_KEY = 4096u,     // (hop record only) the record's value word is the list key (with KEY_PSUB), not a link
+  HOP_ORIGIN = 8192u,  // (hop record only) the value word is still the link k_seg_props wrote, and that link
+                       // is the ORIGIN's segment: the item's winner slot is g_maxchild[value]. Path halving
+                       // clears the bit with the link it replaces (k_resolve then takes the slot from g_origin)
 };
-// bit 31 of the climbing keys (g_tmp) between k_seg_props and k_resolve: the list is a YMap entry
-// (key slots < 2^31); g_key holds the final slots without it
+constexpr uint32_t HOP_ONLY = SEG_HASRO | HOP_KEY | HOP_ORIGIN;  // never in g_flags
+// bit 31 of the climbing keys (g_hop's value word under HOP_KEY) between k_seg_props and k_resolve:
+// the list is a YMap entry (key slots < 2^31); g_key holds the final slots without it
 constexpr uint32_t KEY_PSUB = 0x80000000u;
+// The hop record. A root holds {flags | HOP_KEY, key | KEY_PSUB?}, every other item {flags, link} (a
+// root that got no key links to itself), a GC segment {flags, NONE}. Key and link share the value
+// word, so a record is only ever read or written as ONE 64-bit access (relaxed, workgroup scope: the
+// cache behaviour of a plain access, and never split into two words): a reader sees a whole record
+// some writer stored, never a key beside the flags of a link.
+__device__ __forceinline__ unsigned long long hop_pack(uint32_t flags, uint32_t value) {
+  return ((unsigned long long)value << 32) | flags;
+}
+__device__ __forceinline__ unsigned long long hop_ld(const unsigned long long* p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+__device__ __forceinline__ void hop_st(unsigned long long* p, uint32_t flags, uint32_t value) {
+  __hip_atomic_store(p, hop_pack(flags, value), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
 // key flags
 enum : uint32_t {
   KF_PSUB = 1u,        // the list is a YMap entry (items carry a parentSub)
