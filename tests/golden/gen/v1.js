@@ -51,23 +51,28 @@ function writeVu(out, n) {
   out.push(n & 0x7f);
 }
 
-// Skips the struct section; returns {end, items, structs, clients}
-function skipStructs(r) {
-  let items = 0; let structs = 0;
+// Skips the struct section; returns {items, structs, clients, gcs, parents}: gcs counts GC structs,
+// parents lists the items that name their parent by id as {client, clock, parent: [client, clock]}.
+// onSection(n, client, clock) / onStruct(ref, start, end, len) see every section and struct.
+function skipStructs(r, onSection, onStruct) {
+  let items = 0; let structs = 0; let gcs = 0;
+  const parents = [];
   const nClients = r.vu();
   const clients = [];
   for (let c = 0; c < nClients; c++) {
     const n = r.vu(); const client = r.vu(); let clock = r.vu();
     clients.push(client);
+    if (onSection) onSection(n, client, clock);
     for (let i = 0; i < n; i++) {
+      const start = r.p;
       const info = r.u8();
       const ref = info & 31;
       structs++;
-      if (ref === 0 || ref === 10) { const len = r.vu(); if (ref === 0) items += len; clock += len; continue; }
+      if (ref === 0 || ref === 10) { const len = r.vu(); if (ref === 0) { items += len; gcs++; } clock += len; if (onStruct) onStruct(ref, start, r.p, len); continue; }
       if (info & 0x80) { r.vu(); r.vu(); }
       if (info & 0x40) { r.vu(); r.vu(); }
       if ((info & 0xc0) === 0) {
-        if (r.vu() === 1) r.vstr(); else { r.vu(); r.vu(); }
+        if (r.vu() === 1) r.vstr(); else parents.push({ client, clock, parent: [r.vu(), r.vu()] });
         if (info & 0x20) r.vstr();
       }
       let len = 1;
@@ -84,9 +89,10 @@ function skipStructs(r) {
         default: throw new Error('bad content ref ' + ref);
       }
       items += len; clock += len;
+      if (onStruct) onStruct(ref, start, r.p, len);
     }
   }
-  return { items, structs, clients };
+  return { items, structs, clients, gcs, parents };
 }
 
 function readDs(r) {
@@ -132,6 +138,29 @@ function canonicalSv(sv) {
   return Uint8Array.from(out);
 }
 
+// The update with adjacent GC structs of one client section merged into one; every other byte as
+// it stands (tests/v1util.py coalesce_gc is the same rule, written separately).
+function coalesceGc(u) {
+  const r = new Reader(u);
+  const secs = [];
+  skipStructs(r, (n, client, clock) => secs.push({ client, clock, structs: [] }), (ref, start, end, len) => {
+    const st = secs[secs.length - 1].structs;
+    const last = st[st.length - 1];
+    if (ref === 0 && typeof last === 'number') st[st.length - 1] = last + len;
+    else st.push(ref === 0 ? len : u.subarray(start, end));
+  });
+  const out = [];
+  writeVu(out, secs.length);
+  for (const s of secs) {
+    writeVu(out, s.structs.length); writeVu(out, s.client); writeVu(out, s.clock);
+    for (const x of s.structs) {
+      if (typeof x === 'number') { out.push(0); writeVu(out, x); } else for (const b of x) out.push(b);
+    }
+  }
+  for (const b of u.subarray(r.p)) out.push(b);
+  return Uint8Array.from(out);
+}
+
 function updateStats(u) {
   const r = new Reader(u);
   const s = skipStructs(r);
@@ -141,4 +170,4 @@ function updateStats(u) {
 
 const hex = (u) => Buffer.from(u).toString('hex');
 
-module.exports = { Reader, writeVu, canonicalUpdate, canonicalSv, updateStats, hex };
+module.exports = { Reader, writeVu, canonicalUpdate, canonicalSv, coalesceGc, updateStats, hex };
