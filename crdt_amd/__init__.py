@@ -169,6 +169,22 @@ class JsonStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class CacheStats(ctypes.Structure):  # ycrdt_cache_stats
+    _fields_ = [
+        ("docs_device", ctypes.c_uint64),
+        ("docs_single", ctypes.c_uint64),
+        ("docs_empty", ctypes.c_uint64),
+        ("roots", ctypes.c_uint64),
+        ("out_bytes", ctypes.c_uint64),
+        ("depth_max", ctypes.c_uint32),
+        ("name_max", ctypes.c_uint32),
+        ("device_ms", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class StoreStats(ctypes.Structure):
     _fields_ = [
         ("groups_device", ctypes.c_uint64),
@@ -202,7 +218,7 @@ EXPORTS = (
     "ycrdt_comm_unique_id", "ycrdt_comm_create", "ycrdt_comm_destroy", "ycrdt_batch_merge_sharded",
     "ycrdt_comm_sv_allreduce_max", "ycrdt_comm_ds_allgather", "ycrdt_comm_create_exchange", "ycrdt_route",
     "ycrdt_comm_fleet_sv_allreduce_max", "ycrdt_docs_states_packed", "ycrdt_comm_allgather", "ycrdt_device_count",
-    "ycrdt_docs_diff", "ycrdt_docs_json", "ycrdt_docs_read", "ycrdt_docs_write",
+    "ycrdt_docs_diff", "ycrdt_docs_json", "ycrdt_docs_read", "ycrdt_docs_write", "ycrdt_docs_cache",
     "ycrdt_merge_updates_groups", "ycrdt_updates_state_vectors", "ycrdt_update_state_vector",
 )
 
@@ -284,6 +300,7 @@ def lib():
     L.ycrdt_route.argtypes = [ctypes.c_char_p, sz, u32]
     L.ycrdt_docs_diff.argtypes = [vp, P(vp), P(_Buf), sz, P(_Out), P(ctypes.c_uint64), P(SyncStats)]
     L.ycrdt_docs_json.argtypes = [vp, P(vp), P(cs), P(i32), sz, P(_Out), P(ctypes.c_uint64), P(JsonStats)]
+    L.ycrdt_docs_cache.argtypes = [vp, P(vp), sz, cs, P(_Out), P(ctypes.c_uint64), P(CacheStats)]
     L.ycrdt_docs_read.argtypes = [vp, P(_Read), sz, P(_Out), P(ctypes.c_uint64), P(ctypes.c_int32), P(ctypes.c_uint64), P(ReadStats)]
     L.ycrdt_docs_write.argtypes = [vp, P(_Write), sz, P(_Out), P(ctypes.c_uint64), P(ctypes.c_int32), P(WriteStats)]
     L.ycrdt_merge_updates_groups.argtypes = [vp, P(_Buf), P(u32), sz, u32, P(_Out), P(ctypes.c_uint64), P(StoreStats)]
@@ -917,6 +934,36 @@ def docs_json_stats(docs, roots, kinds, engine=None):
 def docs_json(docs, roots, kinds, engine=None) -> list:
     """[d.root_json(root, kind) for d, root, kind in zip(docs, roots, kinds)] in one device pass (docs_json_stats)."""
     return docs_json_stats(docs, roots, kinds, engine)[0]
+
+
+def docs_cache_stats(docs, index="ix", engine=None):
+    """(texts, stats): for every document the JSON text of crdt.js's cache object `c` in one device
+    pass (ycrdt_docs_cache) — the loop of crdt.js:201-216 / 297-305 batched over documents:
+    { name: (val == 'map' ? doc.getMap(name) : doc.getArray(name)).toJSON() for name, val in the
+    document's index map `index` }, the index read on the device. A document may repeat. stats:
+    ycrdt_cache_stats as a dict (which path the documents took)."""
+    import numpy as np
+
+    n = len(docs)
+    eng = engine or (docs[0].engine if docs else default_engine())
+    hv = np.fromiter((d._h.value for d in docs), dtype=np.uint64, count=n) if n else np.zeros(1, np.uint64)
+    hs = hv.ctypes.data_as(ctypes.POINTER(ctypes.c_void_p))
+    offs = np.zeros(n + 1, dtype=np.uint64)
+    out = _Out()
+    st = CacheStats()
+    _check(lib().ycrdt_docs_cache(eng._h, hs, n, None if index is None else index.encode(), ctypes.byref(out),
+                                  offs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ctypes.byref(st)))
+    try:
+        o = offs.tolist()
+        blob = ctypes.string_at(out.ptr, out.len) if out.len else b""
+        return [blob[o[i]:o[i + 1]].decode() for i in range(n)], st.as_dict()
+    finally:
+        lib().ycrdt_free(ctypes.byref(out))
+
+
+def docs_cache(docs, index="ix", engine=None) -> list:
+    """The JSON text of every document's cache object `c` in one device pass (docs_cache_stats)."""
+    return docs_cache_stats(docs, index, engine)[0]
 
 
 def docs_read_stats(reads, engine=None):

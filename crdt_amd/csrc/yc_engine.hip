@@ -25,6 +25,7 @@
 #include "yc_comm.h"
 #include "yc_sync.h"
 #include "yc_json.h"
+#include "yc_cache.h"
 #include "yc_read.h"
 #include "yc_write.h"
 #include "yc_store.h"
@@ -3453,6 +3454,196 @@ int ycrdt_docs_json(ycrdt_engine* e, ycrdt_doc* const* docs, const char* const* 
     }
     text[i] = &it->second;
     ++S.pairs_single;
+  }
+  uint64_t total = 0;
+  for (size_t i = 0; i < n; ++i) { offs[i] = total; total += text[i]->size(); }
+  offs[n] = total;
+  uint8_t* out = (uint8_t*)malloc(total ? total : 1);
+  if (!out) return fail(YCRDT_E_CAPACITY, "host allocation failed");
+  for (size_t i = 0; i < n; ++i) memcpy(out + offs[i], text[i]->data(), text[i]->size());
+  blob->ptr = out;
+  blob->len = total;
+  S.out_bytes = total;
+  if (st) *st = S;
+  return YCRDT_OK;
+}
+
+// ---- fleet cache refresh (ycrdt_docs_cache; yc_cache.hip)
+static int ensure_view(ycrdt_doc* d);
+namespace {
+
+struct CacheWant {           // one distinct document of the device path
+  std::string text;
+  bool refused = false, done = false;
+};
+
+// One device pass of ycrdt_docs_cache: the toJSON front half over the documents dl with one request
+// per document, (document, index, map), then the cache kernels and the toJSON placement and write.
+// ws[j] is the want of dl[j]. A document the device flags — or every document, when the front half
+// refuses the batch — is left `refused` for the host composition.
+int cache_pass(ycrdt_engine* e, const std::vector<ycrdt_doc*>& dl, const std::string& index, std::vector<CacheWant>& wants,
+               const std::vector<size_t>& ws, uint64_t& roots, double& device_ms) {
+  auto refuse_all = [&]() { for (size_t k : ws) wants[k].refused = true; return YCRDT_OK; };
+  const uint32_t nd = (uint32_t)dl.size();
+  // request d is document d: the root keys ascend with the document
+  std::vector<JsonReq> reqs(nd);
+  const std::vector<uint8_t> names(index.begin(), index.end());
+  const uint64_t ih = fnv_key((const uint8_t*)index.data(), 0, (uint32_t)index.size()) >> 1;  // as k_jsort_key hashes the root names
+  for (uint32_t d = 0; d < nd; ++d) reqs[d] = JsonReq{(1ull << 63) | ((uint64_t)d << 32) | ih, 0, (uint32_t)index.size(), 0, 0};
+  JsonExtra X;
+  X.ws_fixed = 16 * 64;
+  X.ws_per_key = 4 * 6 + 8;  // live | lrank | mixed | smixed | msize | mkind, moffs
+  JsonFront F;
+  if (const int rc = json_front(e, dl, reqs, names, X, F)) return rc;
+  if (F.refused) return refuse_all();
+  JsonArgs& A = F.A;
+  auto& V = e->bufs;
+  bool ok = true;
+  hipStream_t s = e->stream;
+  const uint64_t ck = A.ck;
+  uint64_t at = 0;
+  auto lay = [&](uint64_t bytes) { const uint64_t o = at; at = (at + bytes + 63) & ~uint64_t(63); return o; };
+  const uint64_t o_roots = lay(4), o_live = lay(4 * (ck + 1)), o_lrank = lay(4 * (ck + 1)), o_mixed = lay(4 * (ck + 1));
+  const uint64_t o_smixed = lay(4 * (ck + 1)), o_msize = lay(4 * (ck + 1)), o_moffs = lay(8 * (ck + 1)), o_mkind = lay(4 * ck);
+  CacheArgs C{};
+  C.roots = (uint32_t*)(F.xw + o_roots);
+  C.live = (uint32_t*)(F.xw + o_live);
+  C.lrank = (uint32_t*)(F.xw + o_lrank);
+  C.mixed = (uint32_t*)(F.xw + o_mixed);
+  C.smixed = (uint32_t*)(F.xw + o_smixed);
+  C.msize = (uint32_t*)(F.xw + o_msize);
+  C.moffs = (uint64_t*)(F.xw + o_moffs);
+  C.mkind = (uint32_t*)(F.xw + o_mkind);
+  C.j = A;
+  HIPCHK(hipMemsetAsync(C.roots, 0, 4, s));
+  launch_cache_mark(C, s);
+  scan_u32(F.tmp, F.tmpb, C.live, C.lrank, ck + 1, s);
+  scan_u32(F.tmp, F.tmpb, C.mixed, C.smixed, ck + 1, s);
+  launch_cache_members(C, s);
+  scan_u32_to_u64(F.tmp, F.tmpb, C.msize, C.moffs, ck + 1, s);
+  launch_cache_docs(C, s);
+  scan_u32_to_u64(F.tmp, F.tmpb, A.rsize, A.roffs, (uint64_t)nd + 1, s);
+  // the one size read-back: offsets (the total is the last), document flags, members, the view's counters
+  std::vector<uint8_t> rb(8ull * (nd + 1) + 4ull * nd);
+  Counters c;
+  uint32_t nkeys = 0, nroots = 0;
+  HIPCHK(hipMemcpyAsync(rb.data(), F.W + F.o_rb, rb.size(), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(&c, e->w.ctr, sizeof(Counters), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(&nkeys, F.nkeys, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(&nroots, C.roots, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (c.err || nkeys > ck) return refuse_all();
+  const uint64_t* roffs = (const uint64_t*)rb.data();
+  const uint32_t* rflag = (const uint32_t*)(rb.data() + 8ull * (nd + 1));
+  const uint64_t total = roffs[nd];
+  std::vector<uint8_t> text(total);
+  if (total) {
+    uint8_t* outb = take<uint8_t>(V, B_PACK, total + 64, ok);
+    if (!ok) return fail(YCRDT_E_DEVICE, oom("fleet cache text"));
+    C.j.out = A.out = outb;
+    C.j.out_cap = A.out_cap = total;
+    // braces, names and root positions, then offsets top-down and the members' bytes as toJSON does
+    launch_cache_write(C, s);
+    for (uint32_t level = 0; level <= JSON_DEPTH_MAX; ++level) launch_json_place(A, s);
+    launch_json_write(A, s);
+    HIPCHK(hipEventRecord(e->ev1, s));
+    if (const int rc2 = d2h_span(e, text.data(), outb, total)) return rc2;
+  } else {
+    HIPCHK(hipEventRecord(e->ev1, s));
+  }
+  HIPCHK(hipStreamSynchronize(s));
+  float ms = 0;
+  hipEventElapsedTime(&ms, e->ev0, e->ev1);
+  device_ms += ms;
+  roots += nroots;
+  for (uint32_t d = 0; d < nd; ++d) {
+    CacheWant& q = wants[ws[d]];
+    if (rflag[d] || roffs[d + 1] - roffs[d] < 2) { q.refused = true; continue; }
+    q.text.assign((const char*)text.data() + roffs[d], roffs[d + 1] - roffs[d]);
+    q.done = true;
+  }
+  return YCRDT_OK;
+}
+
+uint64_t cache_pass_bytes() {  // (tests shrink a pass through YCRDT_DOCS_CACHE_PASS_BYTES, as YCRDT_DOCS_JSON_PASS_BYTES does)
+  const char* v = getenv("YCRDT_DOCS_CACHE_PASS_BYTES");
+  const uint64_t x = v ? strtoull(v, nullptr, 10) : 0;
+  return x ? std::min(x, JSON_PASS_BYTES) : JSON_PASS_BYTES;
+}
+
+}  // namespace
+
+int ycrdt_docs_cache(ycrdt_engine* e, ycrdt_doc* const* docs, size_t n, const char* index, ycrdt_out* blob, uint64_t* offs,
+                     ycrdt_cache_stats* st) {
+  if (!e || !docs || !blob || !offs) return fail(YCRDT_E_ARG, "null arg");
+  if (const int rc = check_docs(e, docs, n)) return rc;
+  const std::string ix = index ? index : "ix";
+  blob->ptr = nullptr;
+  blob->len = 0;
+  offs[0] = 0;
+  ycrdt_cache_stats S{};
+  S.depth_max = JSON_DEPTH_MAX;
+  S.name_max = JSON_NAME_MAX;
+  if (st) *st = S;
+  if (n == 0) {
+    blob->ptr = (uint8_t*)malloc(1);
+    if (!blob->ptr) return fail(YCRDT_E_CAPACITY, "host allocation failed");
+    return YCRDT_OK;
+  }
+  if (n >= 0x7FFFFFFFull) return fail(YCRDT_E_CAPACITY, "too many documents");
+  HIPCHK(hipSetDevice(e->device));
+  if (const int rc = flush_queued(e, docs, n)) return rc;
+  // which path every document takes; the device path's distinct documents
+  enum : uint8_t { K_SINGLE = 0, K_EMPTY, K_DEV };
+  const bool off = env_off("YCRDT_DOCS_CACHE");
+  std::vector<uint8_t> kind(n, K_SINGLE);
+  std::vector<size_t> want_of(n, 0);
+  std::unordered_map<const ycrdt_doc*, size_t> dix;
+  std::vector<ycrdt_doc*> dlist;
+  for (size_t i = 0; i < n; ++i) {
+    ycrdt_doc* d = docs[i];
+    if (off || d->ing.has_pending || d->ing.has_ds || e->compat == 135) continue;
+    if (!d->state_len) { kind[i] = K_EMPTY; continue; }
+    if (d->state_len >= JSON_PASS_BYTES) continue;
+    kind[i] = K_DEV;
+    auto it = dix.find(d);
+    if (it == dix.end()) { it = dix.emplace(d, dlist.size()).first; dlist.push_back(d); }
+    want_of[i] = it->second;
+  }
+  std::vector<CacheWant> wants(dlist.size());
+  // device passes: documents in call order, as many as one window holds
+  {
+    const uint64_t pass_bytes = cache_pass_bytes();
+    size_t j = 0;
+    while (j < dlist.size()) {
+      std::vector<ycrdt_doc*> dl;
+      std::vector<size_t> ws;
+      uint64_t bytes = 0;
+      while (j < dlist.size() && (dl.empty() || bytes + dlist[j]->state_len + 64 <= pass_bytes)) {
+        bytes += (dlist[j]->state_len + 63) & ~size_t(63);
+        dl.push_back(dlist[j]);
+        ws.push_back(j);
+        ++j;
+      }
+      if (const int rc = cache_pass(e, dl, ix, wants, ws, S.roots, S.device_ms)) return rc;
+    }
+  }
+  // everything else composed on the host, one document at a time (a repeated document once)
+  std::unordered_map<const ycrdt_doc*, std::string> singles;
+  std::vector<const std::string*> text(n, nullptr);
+  static const std::string empty_object = "{}";
+  for (size_t i = 0; i < n; ++i) {
+    if (kind[i] == K_EMPTY) { text[i] = &empty_object; ++S.docs_empty; continue; }
+    if (kind[i] == K_DEV && wants[want_of[i]].done) { text[i] = &wants[want_of[i]].text; ++S.docs_device; continue; }
+    auto it = singles.find(docs[i]);
+    if (it == singles.end()) {
+      if (const int rc = ensure_view(docs[i])) return rc;
+      std::string j;
+      view_cache_json(docs[i]->view, ix, j);
+      it = singles.emplace(docs[i], std::move(j)).first;
+    }
+    text[i] = &it->second;
+    ++S.docs_single;
   }
   uint64_t total = 0;
   for (size_t i = 0; i < n; ++i) { offs[i] = total; total += text[i]->size(); }

@@ -12,6 +12,7 @@
 // origin / right origin are read off the view, and the struct is written as Item.write (Y@80416).
 #include "yc_host.h"
 #include "yc_json.h"  // the value text: any_json_text and SegCursor, shared with the fleet toJSON kernels
+#include "yc_cache.h"  // index_kind and the member name prefix, shared with the fleet cache kernels
 
 #include <algorithm>
 #include <array>
@@ -317,6 +318,24 @@ bool view_root_json(const HostView& v, const std::string& name, int kind, std::s
   if (kind == 0) put_entries(c, root_entries_of(v, name), false, out);  // every root list named `name` with a parentSub
   else array_json(c, v.root_list(name, nullptr), out);
   return true;
+}
+
+void view_cache_json(const HostView& v, const std::string& index, std::string& out) {
+  out.assign("{");
+  std::string member, err;
+  if (const auto* ks = root_entries_of(v, index))
+    for (uint32_t ki : *ks) {
+      const ViewKey& K = v.keys[ki];
+      if (!entry_live(K)) continue;
+      if (out.size() != 1) out.push_back(',');
+      JString w{out};
+      cache_put_name(w, v.bytes.data() + K.psub_pos, K.psub_len);
+      const ViewSeg& s = K.win;
+      const bool map = s.b0 <= s.b1 && s.b1 <= v.bytes.size() && index_kind(v.bytes.data(), s.b0, s.b1, s.ref);
+      view_root_json(v, v.str(K.psub_pos, K.psub_len), map ? 0 : 1, member, err);
+      out += member;
+    }
+  out.push_back('}');
 }
 
 // toJSON of one shared type: a root type (view_root_json), or the YMap / YArray stored in root map

@@ -35,6 +35,13 @@ struct HostView {
 // toJSON of root `name`: kind 0 = YMap, 1 = YArray (JSON.stringify text)
 bool view_root_json(const HostView& v, const std::string& name, int kind, std::string& out, std::string& err);
 
+// The cache object `c` of crdt.js for index root `index`: one member per live entry of that root map
+// (an entry whose value is undefined included), in the member order of view_root_json, each
+// "name": followed by view_root_json of the root the entry names, as a map when the entry's value
+// == 'map' (index_kind, yc_cache.h) and as an array otherwise. The fleet cache kernels
+// (yc_cache.hip) write the same bytes.
+void view_cache_json(const HostView& v, const std::string& index, std::string& out);
+
 // type_ref of the live shared type stored in root map `root` under `key` (YMap.get returning a
 // Y.AbstractType), or -1 when the key holds a plain value or nothing
 int view_type_at(const HostView& v, const std::string& root, const std::string& key);

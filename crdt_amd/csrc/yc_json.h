@@ -417,8 +417,8 @@ void launch_json_write(const JsonArgs& a, hipStream_t s);
 
 }  // namespace yc
 #ifdef YC_JSON_DEVICE
-// ---- device helpers over JsonArgs, shared by the toJSON kernels (yc_json.hip) and the point-read
-// kernels (yc_read.hip)
+// ---- device helpers over JsonArgs, shared by the toJSON kernels (yc_json.hip), the point-read
+// kernels (yc_read.hip) and the cache kernels (yc_cache.hip)
 namespace yc {
 namespace {
 
@@ -481,6 +481,20 @@ __device__ __forceinline__ bool list_range(const JsonArgs& a, uint32_t kp, uint3
   x0 = K.seg0;
   x1 = K.seg0 + K.nseg;
   return true;
+}
+
+// the item range of a request's root container: keys [lo, hi) of its group (kind 0), or the
+// segments of the root's list (kind 1; kp = its key, VNONE: no such list)
+__device__ __forceinline__ void root_range(const JsonArgs& a, const JsonReq& q, uint32_t& lo, uint32_t& hi, uint32_t& kp) {
+  lo = lower_bound_u64(a.gk, a.ck, q.rkey);
+  hi = upper_bound_u64(a.gk, a.ck, q.rkey);
+  kp = VNONE;
+  if (q.kind == 0) return;
+  kp = first_list(a, lo, hi);
+  uint32_t x0 = 0, x1 = 0;
+  if (kp != VNONE && !list_range(a, kp, x0, x1)) kp = VNONE;
+  lo = a.ck + x0;
+  hi = a.ck + x1;
 }
 
 __device__ __forceinline__ Box type_box(const JsonArgs& a, uint32_t unit, uint32_t tr) {

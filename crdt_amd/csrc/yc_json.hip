@@ -173,20 +173,6 @@ __global__ void k_jsize(JsonArgs a, uint32_t round) {
   a.unres[i] = st != JS_SIZED;
 }
 
-// the item range of a request's root container: keys [lo, hi) of its group (kind 0), or the
-// segments of the root's list (kind 1; kp = its key, VNONE: no such list)
-__device__ __forceinline__ void root_range(const JsonArgs& a, const JsonReq& q, uint32_t& lo, uint32_t& hi, uint32_t& kp) {
-  lo = lower_bound_u64(a.gk, a.ck, q.rkey);
-  hi = upper_bound_u64(a.gk, a.ck, q.rkey);
-  kp = VNONE;
-  if (q.kind == 0) return;
-  kp = first_list(a, lo, hi);
-  uint32_t x0 = 0, x1 = 0;
-  if (kp != VNONE && !list_range(a, kp, x0, x1)) kp = VNONE;
-  lo = a.ck + x0;
-  hi = a.ck + x1;
-}
-
 __global__ void k_jrequests(JsonArgs a) {
   const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r > a.nreq) return;

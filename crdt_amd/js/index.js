@@ -323,6 +323,25 @@ function rootsToJSON(docs, names, kinds) {
   return binding.docsJson(docs.map((d) => d._h), names, codes).map((t) => JSON.parse(t));
 }
 
+// batch entry (not in Yjs): the cache object `c` of crdt.js for every doc in one device pass — the
+// whole open / refresh loop of crdt.js:201-216, 297-305 for many documents after a fleet ingest:
+//   for (const [key, val] of Object.entries(doc.getMap(indexName).toJSON()))
+//     c[key] = (val == 'map' ? doc.getMap(key) : doc.getArray(key)).toJSON()
+// with every doc's index map read on the device, so the caller needs no root names. indexName
+// defaults to 'ix'. A doc may repeat. cachesToJSONText gives the JSON texts unparsed, for callers
+// that forward them. (The text orders members by name bytes; JSON.parse moves integer-like names
+// to the front, as Object.entries over Yjs's own object does.)
+function cachesToJSONText(docs, indexName) {
+  if (!Array.isArray(docs) || (indexName !== undefined && indexName !== null && typeof indexName !== 'string')) {
+    throw new TypeError('cachesToJSON(docs[], indexName?)');
+  }
+  for (const d of docs) settle(d);
+  return binding.docsCache(docs.map((d) => d._h), indexName === undefined ? null : indexName);
+}
+function cachesToJSON(docs, indexName) {
+  return cachesToJSONText(docs, indexName).map((t) => JSON.parse(t));
+}
+
 // batch entry (not in Yjs): many point reads in one device pass — getMap(root).get(key) / .size and
 // getArray(root).get(index) / .length, or the same on the type stored under root map key `parentKey`
 // — the `h[name].get(key)` / `.length` reads of crdt.js:423-430 for many documents after a fleet
@@ -399,6 +418,8 @@ module.exports = {
   encodeStateVector,
   encodeStatesAsUpdates,
   rootsToJSON,
+  cachesToJSON,
+  cachesToJSONText,
   readMany,
   writeMany,
   mergeUpdates: (updates) => binding.mergeUpdates(updates),

@@ -679,6 +679,55 @@ static napi_value js_docs_json(napi_env env, napi_callback_info info) {
   return arr;
 }
 
+/* docsCache(docs[], index | null) → string[]   (the text of crdt.js's cache object `c` of every
+ * document in one device pass, ycrdt_docs_cache: the loop of crdt.js:201-216 / 297-305 batched over
+ * documents, the index map read on the device; null: the index root "ix") */
+static napi_value js_docs_cache(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  bool a0 = false;
+  if (argc >= 1) napi_is_array(env, argv[0], &a0);
+  uint32_t n = 0;
+  if (a0) napi_get_array_length(env, argv[0], &n);
+  char *index = NULL;
+  if (!a0 || (argc >= 2 && !get_str(env, argv[1], &index, 1))) {
+    napi_throw_type_error(env, NULL, "docsCache(docs[], index | null)");
+    return NULL;
+  }
+  ycrdt_engine *e = engine(env);
+  if (!e) { free(index); return NULL; }
+  ycrdt_doc **docs = (ycrdt_doc **)calloc(n ? n : 1, sizeof(ycrdt_doc *));
+  uint64_t *offs = (uint64_t *)calloc((size_t)n + 1, sizeof(uint64_t));
+  int ok = docs && offs;
+  if (!ok) napi_throw_error(env, NULL, "docsCache: out of host memory");
+  for (uint32_t i = 0; ok && i < n; ++i) {
+    napi_value d;
+    napi_get_element(env, argv[0], i, &d);
+    docs[i] = get_doc(env, d);
+    if (!docs[i]) ok = 0;
+  }
+  ycrdt_out blob = {NULL, 0};
+  napi_value arr = NULL;
+  if (ok) {
+    int rc = ycrdt_docs_cache(e, docs, n, index, &blob, offs, NULL);
+    if (rc != YCRDT_OK) {
+      throw_rc(env, rc);
+    } else {
+      if (napi_create_array_with_length(env, n, &arr) != napi_ok) arr = NULL;
+      for (uint32_t i = 0; arr && i < n; ++i) {
+        napi_value s;
+        if (napi_create_string_utf8(env, (const char *)blob.ptr + offs[i], (size_t)(offs[i + 1] - offs[i]), &s) != napi_ok) { arr = NULL; break; }
+        napi_set_element(env, arr, i, s);
+      }
+      ycrdt_free(&blob);
+      if (!arr) napi_throw_error(env, NULL, "ycrdt: N-API call failed: docsCache result");
+    }
+  }
+  free(docs); free(offs); free(index);
+  return arr;
+}
+
 /* docsRead(docs[], ops[], roots[], parentKeys[], keys[], indexes[]) → (string | undefined | number)[]
  * (mapGet / mapSize / arrayGet / arrayLength of every request in one device pass, ycrdt_docs_read:
  * the `h[name].get(key)` / `.length` reads of crdt.js:423-430 batched over documents; ops are
@@ -1101,6 +1150,7 @@ static napi_value init(napi_env env, napi_value exports) {
       {"mapTypeAt", NULL, js_map_type_at, NULL, NULL, NULL, napi_default, NULL},
       {"docJson", NULL, js_doc_json, NULL, NULL, NULL, napi_default, NULL},
       {"docsJson", NULL, js_docs_json, NULL, NULL, NULL, napi_default, NULL},
+      {"docsCache", NULL, js_docs_cache, NULL, NULL, NULL, napi_default, NULL},
       {"docsRead", NULL, js_docs_read, NULL, NULL, NULL, napi_default, NULL},
       {"docsWrite", NULL, js_docs_write, NULL, NULL, NULL, napi_default, NULL},
       {"typeJson", NULL, js_type_json, NULL, NULL, NULL, napi_default, NULL},

@@ -156,6 +156,36 @@ typedef struct {
 } ycrdt_json_stats;
 int ycrdt_docs_json(ycrdt_engine *e, ycrdt_doc *const *docs, const char *const *roots, const int *kinds,
                     size_t n, ycrdt_out *blob, uint64_t *offs, ycrdt_json_stats *st /* may be NULL */);
+/* The cache refresh for many documents in one device pass: the loop of crdt.js:201-216 / 297-305,
+ *   for (const [key, val] of Object.entries(ix.toJSON())) c[key] = (val == 'map' ? doc.getMap(key) : doc.getArray(key)).toJSON()
+ * batched over documents, with every document's index map read on the device. Document i =
+ * blob[offs[i] .. offs[i+1]) is the text of its `c`: one JSON object with one member for every live
+ * entry of root map `index` (NULL: "ix"), an entry whose value is `undefined` included, in the member
+ * order of ycrdt_doc_json(doc, index, 0); each member is the entry's name, escaped as map entry
+ * names are, `:` and exactly ycrdt_doc_json(doc, name, kind), kind 0 iff the entry's value == 'map'
+ * in JavaScript's loose sense (the string, or one-element arrays around it), else 1. No index root,
+ * no live entry or an empty document give {}. offs holds n+1 entries; blob is released with
+ * ycrdt_free. A document may repeat (it is computed once). One (document, index, map) request per
+ * document goes through the fleet toJSON front half; the requests for the listed roots are derived
+ * on the device from the sorted view keys. Empty documents are answered inline.
+ * Documents with pending structs or a pending delete set, engines with compat 135, and documents
+ * the device flags (an index name over name_max bytes, a listed root the toJSON bounds refuse, two
+ * root names in one hash slot) are composed on the host from the same definitions, byte for byte;
+ * YCRDT_DOCS_CACHE=0 sends every document there. Queued applies are flushed first.
+ * docs_device + docs_single + docs_empty == n. n == 0 needs no device. A document of another
+ * engine gives YCRDT_E_ARG and no output. */
+typedef struct {
+  uint64_t docs_device;   /* text written on the device */
+  uint64_t docs_single;   /* composed on the host, one by one */
+  uint64_t docs_empty;    /* empty document: "{}", no device work */
+  uint64_t roots;         /* members written on the device */
+  uint64_t out_bytes;
+  uint32_t depth_max;     /* nested-type levels the device path takes (constant) */
+  uint32_t name_max;      /* longest index or map-entry name (bytes) the device ordering takes (constant) */
+  double device_ms;       /* view, JSON and cache kernels of the passes (the merge before them not included) */
+} ycrdt_cache_stats;
+int ycrdt_docs_cache(ycrdt_engine *e, ycrdt_doc *const *docs, size_t n, const char *index /* NULL: "ix" */,
+                     ycrdt_out *blob, uint64_t *offs /* n+1 */, ycrdt_cache_stats *st /* may be NULL */);
 /* Point reads for many documents in one device pass: the `h[name].has(key)` / `.get(key)` /
  * `.length` reads of crdt.js:423-430 batched over documents. Read i gives exactly what the single
  * call gives for the same arguments. MAP_GET / ARRAY_GET: states[i] is ycrdt_map_get's /
