@@ -10,6 +10,7 @@
 // Every size is computed first (one lane per output struct / run / client), positions come from
 // exclusive scans, then a second pass writes the bytes.
 #include "yc_work.h"
+#include "yc_encrec.h"
 
 namespace yc {
 
@@ -49,12 +50,15 @@ __device__ uint32_t encode_struct_general(const Work& w, uint32_t nclients, uint
 // length). So it is a copy of [pos + 1, cpos) and [cpos, cend) — five columns instead of the
 // general path's twenty (and its reference-client lookups).
 // (output struct = segments [a, b))
+// Sizing (!WRITE) with `rec` given, it also leaves the struct's encode record there (yc_encrec.h;
+// 0 when the widths do not fit or records are off): the write pass then needs none of these columns.
 // ENC_DEFER: not the whole-item case; the general encoder takes it in a kernel of its own
 // (k_out_sizes_general / k_write_general): inlined, the general path's registers — 74 / 94 VGPRs —
 // cost the one-pass kernels two to three waves per SIMD for every output struct
 constexpr uint32_t ENC_DEFER = 0xFFFFFFFFu;
 template <bool WRITE>
-__device__ __forceinline__ uint32_t encode_struct_fast(const Work& w, uint32_t a, uint32_t b, uint8_t* __restrict__ out, uint64_t p0) {
+__device__ __forceinline__ uint32_t encode_struct_fast(const Work& w, uint32_t a, uint32_t b, uint8_t* __restrict__ out, uint64_t p0,
+                                                       uint64_t* rec = nullptr) {
   if (b == a + 1 && !w.delta) {
     const uint32_t f = w.g_flags[a], src = w.g_src[a], ga = seg_start(w, a), gb = seg_start(w, b);
     const uint32_t slen = w.s_len[src], spos = w.s_pos[src], scpos = w.s_cpos[src], scend = w.s_cend[src];
@@ -62,10 +66,14 @@ __device__ __forceinline__ uint32_t encode_struct_fast(const Work& w, uint32_t a
     if ((f & (SEG_ITEM | SEG_EXPLICIT)) == (SEG_ITEM | SEG_EXPLICIT) && gb - ga == slen && !(spk & 0xC0u)) {
       const bool del = (f & SEG_DEL) != 0;
       const uint32_t hdr = scpos - spos - 1;  // origin / right origin / parent / parentSub bytes
-      if (!WRITE) return 1 + hdr + (del ? vu_size(slen) : scend - scpos);
+      const uint32_t info = (del ? (uint32_t)REF_DELETED : (info0 & 31u)) | (info0 & 0xC0u) | ((f & SEG_PSUB) ? 0x20u : 0u);
+      if (!WRITE) {
+        if (rec && w.enc_record) *rec = rec_pack(spos, info, del, hdr, del ? slen : scend - scpos);
+        return 1 + hdr + (del ? vu_size(slen) : scend - scpos);
+      }
       const uint8_t* __restrict__ sb = struct_bytes(w, src);
       uint64_t p = p0;
-      out[p++] = (uint8_t)((del ? (uint32_t)REF_DELETED : (info0 & 31u)) | (info0 & 0xC0u) | ((f & SEG_PSUB) ? 0x20u : 0u));
+      out[p++] = (uint8_t)info;
       p = copy_bytes(out, p, sb + spos + 1, hdr);
       if (del) p = wr_vu(out, p, slen);
       else p = copy_bytes(out, p, sb + scpos, scend - scpos);
@@ -73,6 +81,15 @@ __device__ __forceinline__ uint32_t encode_struct_fast(const Work& w, uint32_t a
     }
   }
   return ENC_DEFER;
+}
+// the same bytes from the struct's record alone (a record exists only in a batch of one window)
+__device__ __forceinline__ void write_struct_record(const Work& w, uint64_t rec, uint8_t* __restrict__ out, uint64_t p) {
+  const EncRec x = rec_unpack(rec);
+  const uint8_t* __restrict__ sb = w.bytes + x.pos;
+  out[p++] = (uint8_t)x.info;
+  p = copy_bytes(out, p, sb + 1, x.hdr);
+  if (x.del) wr_vu(out, p, x.tail);
+  else copy_bytes(out, p, sb + 1 + x.hdr, x.tail);
 }
 
 template <bool WRITE>
@@ -217,8 +234,16 @@ __device__ __forceinline__ uint32_t encode_struct_general(const Work& w, uint32_
 // the merge flags) records it (o_first, o_cidx) and sizes it, finding the struct's end by stepping
 // over the segments merged into it (usually none); the others zero the size slots past NO, so the
 // scan over NS + 1 entries sees exactly the NO sizes.
-__device__ __forceinline__ bool out_sizes_at(const Work& w, uint32_t s, uint32_t nsegs, uint32_t nout) {
+// The first output struct of every client (CC_FIRST_OUT) falls out of the same pass: a segment whose
+// client differs from the one before it always starts an output struct (a merge needs the same
+// client), so it records its output id for its own client and for every client without a segment
+// between the two; the sentinel lane does the same for the clients past the last segment's.
+__device__ __forceinline__ void first_out_fill(const Work& w, uint32_t prev, uint32_t c, uint32_t o) {
+  for (uint32_t k = prev + 1; k <= c; ++k) ccol(w, CC_FIRST_OUT)[k] = o;  // (prev = NONE: from client 0)
+}
+__device__ __forceinline__ bool out_sizes_at(const Work& w, uint32_t s, uint32_t nsegs, uint32_t nclients, uint32_t nout) {
   if (s == nsegs) {
+    first_out_fill(w, nsegs ? w.g_cidx[nsegs - 1] : NONE, nclients, nout);
     w.o_first[nout] = nsegs;  // sentinel
     w.o_size[nsegs] = 0;
     w.ctr->nout = nout;
@@ -226,6 +251,8 @@ __device__ __forceinline__ bool out_sizes_at(const Work& w, uint32_t s, uint32_t
   }
   const uint32_t o = w.g_outid[s];
   const bool start = !(w.g_flags[s] & SEG_MERGE);
+  const uint32_t cidx = w.g_cidx[s], cprev = s ? w.g_cidx[s - 1] : NONE;
+  if (cidx != cprev) first_out_fill(w, cprev, cidx, o);
   uint32_t sz = 0;
   if (!start) {
     w.o_size[nout + (s - o)] = 0;  // (s - o: its rank among the non-starts)
@@ -233,8 +260,10 @@ __device__ __forceinline__ bool out_sizes_at(const Work& w, uint32_t s, uint32_t
     uint32_t b = s + 1;
     while (b < nsegs && (w.g_flags[b] & SEG_MERGE)) ++b;
     w.o_first[o] = s;
-    w.o_cidx[o] = w.g_cidx[s];
-    sz = encode_struct_fast<false>(w, s, b, nullptr, 0);
+    w.o_cidx[o] = cidx;
+    uint64_t rec = 0;  // (stays 0: deferred, too wide, or records off)
+    sz = encode_struct_fast<false>(w, s, b, nullptr, 0, &rec);
+    w.o_rec[o] = sz ? rec : 0ull;
     // a deferred one (k_out_sizes_general) is flagged, not listed: one list counter taken by a
     // wavefront of every few took C4 (mostly merged runs) 1.7 -> 7.3 ms, at the one-word atomic rate
     w.o_size[o] = sz == ENC_DEFER ? 0u : sz;
@@ -245,7 +274,7 @@ __device__ __forceinline__ bool out_sizes_at(const Work& w, uint32_t s, uint32_t
 __global__ __launch_bounds__(256) void k_out_sizes(Work w, uint32_t nsegs, uint32_t nclients) {
   const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s > nsegs) return;
-  const bool defer = out_sizes_at(w, s, nsegs, nsegs ? w.g_outid[nsegs] : 0u);
+  const bool defer = out_sizes_at(w, s, nsegs, nclients, nsegs ? w.g_outid[nsegs] : 0u);
   wave_flag(&w.ctr->pad[6], defer);  // (the general kernels run only when some struct is deferred)
 }
 // the deferred output structs (split, merged or delta-cut ones), sized by the general encoder
@@ -318,15 +347,10 @@ __global__ __launch_bounds__(RUNS_LANES) void k_runs_small(Work w, uint32_t nseg
   block_scan_u32<RUNS_LANES>(w.r_size, w.r_pos, nsegs + 1, part);
 }
 
-// per client: first output struct and first delete-set run, from the boundaries of the (client-
-// sorted) output and run arrays — one parallel pass instead of per-client binary searches, whose
-// ~80 dependent loads per lane made the per-client pass latency-bound
-__device__ __forceinline__ void client_bounds_at(const Work& w, uint32_t i, uint32_t nclients, uint32_t nout, uint32_t nruns) {
-  if (i <= nout) {
-    const int64_t a = i == 0 ? -1 : (int64_t)w.o_cidx[i - 1];
-    const int64_t b = i == nout ? (int64_t)nclients : (int64_t)w.o_cidx[i];
-    for (int64_t c = a + 1; c <= b; ++c) ccol(w, CC_FIRST_OUT)[c] = i;
-  }
+// per client: first delete-set run, from the boundaries of the (client-sorted) run array — one
+// parallel pass instead of per-client binary searches, whose ~80 dependent loads per lane made the
+// per-client pass latency-bound (the first output struct comes from the size pass, out_sizes_at)
+__device__ __forceinline__ void client_bounds_at(const Work& w, uint32_t i, uint32_t nclients, uint32_t nruns) {
   if (i <= nruns) {
     const int64_t a = i == 0 ? -1 : (int64_t)w.g_cidx[w.r_seg[i - 1]];
     const int64_t b = i == nruns ? (int64_t)nclients : (int64_t)w.g_cidx[w.r_seg[i]];
@@ -335,7 +359,7 @@ __device__ __forceinline__ void client_bounds_at(const Work& w, uint32_t i, uint
 }
 __global__ void k_client_bounds(Work w, uint32_t nclients, uint32_t nsegs) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i <= nsegs) client_bounds_at(w, i, nclients, w.ctr->nout, w.g_tmp2[nsegs]);
+  if (i <= nsegs) client_bounds_at(w, i, nclients, w.g_tmp2[nsegs]);  // (lanes past the run count: one load)
 }
 
 // per client: struct block + delete-set block + state-vector entry sizes; returns bit 0: the
@@ -402,6 +426,12 @@ __global__ void k_reverse3(Work w, uint32_t nclients) {
   const uint32_t src[3] = {CC_BLK, CC_DSBLK, CC_SV}, dst[3] = {CC_REV, CC_REV2, CC_REV3};
   for (int k = 0; k < 3; ++k) ccol(w, dst[k])[i] = i < nclients ? ccol(w, src[k])[emit_slot_client(w, nclients, k, i)] : 0;
 }
+// where client c's first included struct goes and that struct's o_pos: all out_pos needs of a client
+__device__ __forceinline__ void out_base_at(const Work& w, uint32_t c, uint32_t nclients, uint64_t blkpos) {
+  const bool incl = c < nclients && ccol(w, CC_NINCL)[c];
+  ccol64(w, CC64_OUTBASE)[c] = incl ? blkpos + ccol(w, CC_HDR)[c] : 0ull;
+  ccol(w, CC_OPOS0)[c] = incl ? w.o_pos[ccol(w, CC_FIRST_INCL)[c]] : 0u;
+}
 __global__ void k_unreverse3(Work w, uint32_t nclients) {
   const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c > nclients) return;
@@ -410,7 +440,9 @@ __global__ void k_unreverse3(Work w, uint32_t nclients) {
   const uint32_t src[3] = {CC64_SCAN, CC64_SCAN2, CC64_SCAN3}, dst[3] = {CC64_BLKPOS, CC64_DSPOS, CC64_SVPOS};
   for (int k = 0; k < 3; ++k) {
     const uint32_t slot = c == nclients ? nclients : (k > 0 && w.cl_emit) ? w.cl_slot[c] : nclients - 1 - c;
-    ccol64(w, dst[k])[c] = ccol64(w, src[k])[slot];
+    const uint64_t pos = ccol64(w, src[k])[slot];
+    ccol64(w, dst[k])[c] = pos;
+    if (k == 0) out_base_at(w, c, nclients, pos);
   }
 }
 
@@ -430,13 +462,16 @@ __global__ void k_totals(Work w, uint32_t nclients) { totals_body(w, nclients); 
 
 __device__ __forceinline__ uint64_t out_pos(const Work& w, uint32_t o) {
   const uint32_t c = w.o_cidx[o];
-  const uint32_t fi = ccol(w, CC_FIRST_INCL)[c];
   // (o_pos wraps at 2^32: differences within one client's block are exact)
-  return w.ctr->pad[3] + ccol64(w, CC64_BLKPOS)[c] + ccol(w, CC_HDR)[c] + (uint32_t)(w.o_pos[o] - w.o_pos[fi]);
+  return w.ctr->pad[3] + ccol64(w, CC64_OUTBASE)[c] + (uint32_t)(w.o_pos[o] - ccol(w, CC_OPOS0)[c]);
 }
 __global__ __launch_bounds__(256) void k_write_structs(Work w, uint32_t nsegs, uint32_t nclients) {
   const uint32_t o = blockIdx.x * blockDim.x + threadIdx.x;
   if (o >= w.ctr->nout || w.ctr->pad[5]) return;
+  // the common struct: its record, position and client in one round of loads, two per-client words
+  // in the next, then the source bytes
+  const uint64_t rec = w.o_rec[o];
+  if (rec_valid(rec)) { write_struct_record(w, rec, w.out, out_pos(w, o)); return; }
   if (w.o_size[o] == 0) return;
   // (the deferred ones decline here, k_write_general writes them)
   encode_struct_fast<true>(w, w.o_first[o], w.o_first[o + 1], w.out, out_pos(w, o));
@@ -523,7 +558,9 @@ __device__ __forceinline__ void layout_small_body(const Work& w, uint32_t nclien
   for (uint32_t c = t; c <= nclients; c += LAYOUT_LANES)
     for (int k = 0; k < 3; ++k) {
       const uint32_t slot = c == nclients ? nclients : (k > 0 && w.cl_emit) ? w.cl_slot[c] : nclients - 1 - c;
-      ccol64(w, dst[k])[c] = ccol64(w, scol[k])[slot];
+      const uint64_t pos = ccol64(w, scol[k])[slot];
+      ccol64(w, dst[k])[c] = pos;
+      if (k == 0) out_base_at(w, c, nclients, pos);
     }
   __syncthreads();
   if (t == 0) totals_body(w, nclients);  // (k_totals)
@@ -580,7 +617,7 @@ __global__ __launch_bounds__(ENC_SMALL_LANES) void k_encode_small(Work w, uint32
   block_scan_u32<ENC_SMALL_LANES>(w.r_size, w.r_pos, nsegs + 1, part);
   // output struct sizes (k_out_sizes, k_out_sizes_general)
   const uint32_t nout = nsegs ? w.g_outid[nsegs] : 0u;
-  for (uint32_t s = t; s <= nsegs; s += ENC_SMALL_LANES) out_sizes_at(w, s, nsegs, nout);
+  for (uint32_t s = t; s <= nsegs; s += ENC_SMALL_LANES) out_sizes_at(w, s, nsegs, nclients, nout);
   __syncthreads();
   for (uint32_t o = t; o < nout; o += ENC_SMALL_LANES)
     if (w.o_gen[o]) w.o_size[o] = encode_struct_general<false>(w, nclients, w.o_first[o], w.o_first[o + 1], nullptr, 0);
@@ -588,7 +625,7 @@ __global__ __launch_bounds__(ENC_SMALL_LANES) void k_encode_small(Work w, uint32
   block_scan_u32<ENC_SMALL_LANES>(w.o_size, w.o_pos, nsegs + 1, part);
   // per-client bounds and sizes (k_client_bounds, k_client_sizes)
   const uint32_t nruns = w.g_tmp2[nsegs];
-  for (uint32_t i = t; i <= nsegs; i += ENC_SMALL_LANES) client_bounds_at(w, i, nclients, nout, nruns);
+  for (uint32_t i = t; i <= nsegs; i += ENC_SMALL_LANES) client_bounds_at(w, i, nclients, nruns);
   __syncthreads();
   uint32_t m = 0;
   for (uint32_t c = t; c <= nclients; c += ENC_SMALL_LANES) {
@@ -610,6 +647,7 @@ __global__ __launch_bounds__(ENC_SMALL_LANES) void k_encode_small(Work w, uint32
     if (!w.o_size[o]) continue;
     YC_BOUND(w, out_pos(w, o) + w.o_size[o], w.cap_out + 1, BOUNDS_OUTPUT);
     if (w.o_gen[o]) encode_struct_general<true>(w, nclients, w.o_first[o], w.o_first[o + 1], w.out, out_pos(w, o));
+    else if (rec_valid(w.o_rec[o])) write_struct_record(w, w.o_rec[o], w.out, out_pos(w, o));
     else encode_struct_fast<true>(w, w.o_first[o], w.o_first[o + 1], w.out, out_pos(w, o));
   }
   for (uint32_t c = t; c < max(nclients, 1u); c += ENC_SMALL_LANES) write_clients_at(w, c, nclients);

@@ -444,7 +444,7 @@ void layout(ycrdt_batch* b, const std::vector<Src>& src, std::vector<uint32_t>& 
   b->win_shift = WIN_SHIFT;
   if (const char* ws = getenv("YCRDT_WIN_SHIFT")) {  // tests: small windows (every multi-window path on MBs)
     const int v = atoi(ws);
-    if (v >= 20 && v <= 32) b->win_shift = (uint32_t)v;
+    if (v >= 16 && v <= 32) b->win_shift = (uint32_t)v;  // (64 KiB: a few hundred small updates span several)
   }
   const uint64_t wuse = win_use(b->win_shift);
   uint64_t total = 0, win = 0;  // total: bytes used in window `win`
@@ -1082,6 +1082,8 @@ int run_decode(ycrdt_engine* e, ycrdt_batch* b, bool lazy, Decoded& D, bool gene
                   {(uint32_t*)w.sec_bits, (uint64_t)nwords * 2, 0u}}, s);
   w.dbg_bounds = getenv("YCRDT_DEBUG_BOUNDS") && getenv("YCRDT_DEBUG_BOUNDS")[0] == '1' ? 1u : 0u;
   w.scan_fused = env_off("YCRDT_SCAN_FUSED") ? 0u : 1u;  // (read per merge: A/B in one process)
+  // the encode record (yc_encrec.h) holds a position within ONE window; YCRDT_ENC_RECORD=0: A/B, tests
+  w.enc_record = b->nwin <= 1 && !env_off("YCRDT_ENC_RECORD") ? 1u : 0u;
   w.upre = b->pre_src >= 0 && !b->pre_check ? b->pre_u : NONE;
   if (w.upre != NONE) launch_predecoded(w, b->pre_u, b->pre, false, s);  // (a doc state: its own encode's decode)
   const bool dbg_yata = getenv("YCRDT_DEBUG_YATA") && getenv("YCRDT_DEBUG_YATA")[0] == '1';
@@ -1405,6 +1407,11 @@ int run_merge(ycrdt_engine* e, ycrdt_batch* b, const std::unordered_map<uint32_t
   w.g_origin = take<uint32_t>(V, B_GORIG, U + 1, ok);
   w.g_rorigin = take<uint32_t>(V, B_GRORIG, U + 1, ok);
   w.g_hop = take<unsigned long long>(V, B_GLINK, U + 1, ok);  // 8 B per segment
+  // The encode record of every output struct (NO <= NS <= U entries) lives in the hop records'
+  // buffer: g_hop is read only by seg_props_at and resolve_at (yc_merge.hip; k_seg_props, k_resolve
+  // and the same phases of k_merge_small), which are finished before the encode starts, in the
+  // unsharded and in the sharded merge alike. No other unit reads or takes B_GLINK.
+  w.o_rec = w.g_hop;
   w.g_key = take<uint32_t>(V, B_GKEY, U + 1, ok);
   w.g_maxchild = take<uint32_t>(V, B_GMAXC, U + 1, ok);
   w.g_outid = take<uint32_t>(V, B_GOUTID, U + 2, ok);

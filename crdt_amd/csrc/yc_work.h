@@ -245,6 +245,7 @@ struct Work {
                                    // word (SEG_* | HOP_*), in the high word the list key (HOP_KEY) or the
                                    // link up the origin chain: one 8-B load per climbing hop, always read
                                    // and written whole (hop_ld / hop_st; k_seg_props -> k_resolve)
+                                   // (after k_resolve the buffer holds the encode records, o_rec)
   uint32_t* g_key = nullptr;       // resolved key slot or NONE
   uint32_t* g_maxchild = nullptr;  // seg + 1 of the max-client child (segments are in client order), 0 = none
   uint32_t* g_next = nullptr;      // descent pointer / pointer jumping
@@ -356,6 +357,10 @@ struct Work {
   uint32_t* o_size = nullptr;      // encoded size (0 = below the target state vector)
   uint32_t* o_pos = nullptr;       // [NO+1] exclusive prefix of o_size
   uint8_t* o_gen = nullptr;        // [NO] 1: the general encoder takes the output struct (k_out_sizes_general)
+  unsigned long long* o_rec = nullptr;  // [NO] encode record (yc_encrec.h) of the output structs the whole-item
+                                   // encoder takes, 0 = none (k_out_sizes -> k_write_structs). Aliases g_hop.
+  uint32_t enc_record = 1;         // 0 (YCRDT_ENC_RECORD=0, read per merge; or a batch of several windows): no
+                                   // valid record is written, every struct is encoded from its columns
   uint32_t* r_seg = nullptr;       // [runs] first segment of delete-set run
   uint32_t* r_len = nullptr;       // [runs] run length in units
   uint32_t* r_size = nullptr;      // [runs+1] encoded size of (clock,len)
@@ -677,12 +682,15 @@ __device__ __forceinline__ void bounds_fail(Counters* ctr, uint32_t what) {
 // per-client scratch arrays inside Work::cc
 enum : uint32_t {
   CC_FIRST_OUT = 0, CC_FIRST_INCL, CC_NINCL, CC_HDR, CC_BLK, CC_BLKPOS, CC_NRUNS, CC_FIRST_RUN,
-  CC_DSBLK, CC_DSPOS, CC_SV, CC_SVPOS, CC_REV, CC_REVSCAN, CC_RUN_LO, CC_REV2, CC_REVSCAN2, CC_REV3, CC_REVSCAN3, CC_N
+  CC_DSBLK, CC_DSPOS, CC_SV, CC_SVPOS, CC_REV, CC_REVSCAN, CC_RUN_LO, CC_REV2, CC_REVSCAN2, CC_REV3, CC_REVSCAN3,
+  CC_OPOS0,  // o_pos of the client's first included output struct (out_pos)
+  CC_N
 };
 
 // 64-bit per-client columns inside Work::cc64: the block positions of the struct, delete-set and
 // state-vector sections, and the scans they come from
-enum : uint32_t { CC64_BLKPOS = 0, CC64_DSPOS, CC64_SVPOS, CC64_SCAN, CC64_SCAN2, CC64_SCAN3, CC64_N };
+// (CC64_OUTBASE: the client's block position plus its header size — where its first struct goes)
+enum : uint32_t { CC64_BLKPOS = 0, CC64_DSPOS, CC64_SVPOS, CC64_SCAN, CC64_SCAN2, CC64_SCAN3, CC64_OUTBASE, CC64_N };
 
 // segment flags
 enum : uint32_t {
