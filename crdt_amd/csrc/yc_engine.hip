@@ -2,7 +2,10 @@
 //
 // One translation unit, in this order: buffers and the arena, batch staging, the device passes over a
 // staged batch (decode, merge, view, lazy merge / diff, the per-document split), the doc model, the
-// calls over many documents, the batch and comm ABI, local ops and reads. The helpers that make no HIP call are in yc_engine_host.h (tested on the CPU).
+// calls over many documents (their shared helpers first; json_front and what the toJSON, cache, read
+// and write passes share behind it stand with the toJSON call), the batch and comm ABI, local ops and
+// reads. The helpers that make no HIP call are in yc_engine_host.h (tested on the CPU): state vectors,
+// the marks block, pass bytes and windows, aligned layouts, the answer blob.
 //
 // One engine = one HIP device + one stream + a grow-only set of HBM buffers. A merge runs the
 // decode → dedupe → delete-set → segmentation → map-winner → encode kernels back to back on the
@@ -1080,7 +1083,7 @@ int run_decode(ycrdt_engine* e, ycrdt_batch* b, bool lazy, Decoded& D, bool gene
                   {w.usec_n, (uint64_t)nu + 1, 0u},  // an update no walker reached has no sections
                   {(uint32_t*)w.final_bits, (uint64_t)nwords * 2, 0u},
                   {(uint32_t*)w.sec_bits, (uint64_t)nwords * 2, 0u}}, s);
-  w.dbg_bounds = getenv("YCRDT_DEBUG_BOUNDS") && getenv("YCRDT_DEBUG_BOUNDS")[0] == '1' ? 1u : 0u;
+  w.dbg_bounds = env_on("YCRDT_DEBUG_BOUNDS") ? 1u : 0u;
   w.scan_fused = env_off("YCRDT_SCAN_FUSED") ? 0u : 1u;  // (read per merge: A/B in one process)
   // the encode record (yc_encrec.h) holds a position within ONE window; YCRDT_ENC_RECORD=0: A/B, tests
   w.enc_record = b->nwin <= 1 && !env_off("YCRDT_ENC_RECORD") ? 1u : 0u;
@@ -2723,6 +2726,70 @@ int flush_queued(ycrdt_engine* e, ycrdt_doc* const* docs, size_t n) {
   return flush_multi(e, q);
 }
 
+// Resident state bytes merged per device pass (one 4 GiB window holds them), and the state from
+// which a document is too large for the device path of these calls.
+constexpr uint64_t JSON_PASS_BYTES = uint64_t(1) << 31;
+
+// The path a document takes through such a call: the device pass, the fixed answer of an empty
+// document, or the single calls — when the call's switch is off, the document has pending structs or
+// a pending delete set, the engine mirrors Yjs 13.5, or the state is too large.
+enum DocPath : uint8_t { K_SINGLE = 0, K_EMPTY, K_DEV };
+DocPath doc_path(const ycrdt_engine* e, const ycrdt_doc* d, bool off) {
+  if (off || d->ing.has_pending || d->ing.has_ds || e->compat == 135) return K_SINGLE;
+  if (!d->state_len) return K_EMPTY;
+  return d->state_len >= JSON_PASS_BYTES ? K_SINGLE : K_DEV;
+}
+
+// the index of d among the call's distinct documents `dlist` (call order)
+uint32_t intern_doc(std::unordered_map<const ycrdt_doc*, uint32_t>& dix, std::vector<ycrdt_doc*>& dlist, ycrdt_doc* d) {
+  const auto it = dix.emplace(d, (uint32_t)dlist.size());
+  if (it.second) dlist.push_back(d);
+  return it.first->second;
+}
+
+// the device passes over the documents dlist (pass_windows): pass k takes [cut[k], cut[k + 1])
+std::vector<size_t> doc_windows(const std::vector<ycrdt_doc*>& dlist, uint64_t pass_bytes) {
+  std::vector<uint64_t> lens;
+  for (const ycrdt_doc* d : dlist) lens.push_back(d->state_len);
+  return pass_windows(lens, pass_bytes);
+}
+// ... and the wants of a pass: those of its documents, in document order
+std::vector<size_t> window_wants(const std::vector<std::vector<size_t>>& by_doc, size_t j0, size_t j1) {
+  std::vector<size_t> ws;
+  for (size_t j = j0; j < j1; ++j) ws.insert(ws.end(), by_doc[j].begin(), by_doc[j].end());
+  return ws;
+}
+
+BlobPart part_of(const std::string& s) { return BlobPart{s.data(), s.size()}; }
+BlobPart part_of(const std::vector<uint8_t>& v) { return BlobPart{v.data(), v.size()}; }
+
+// The answer of a call: the parts as one blob (pack_blob), its size also into the stats' out_bytes.
+int give_blob(const std::vector<BlobPart>& parts, ycrdt_out* blob, uint64_t* offs, uint64_t& out_bytes) {
+  uint64_t total = 0;
+  uint8_t* out = pack_blob(parts, offs, total);
+  if (!out) return fail(YCRDT_E_CAPACITY, "host allocation failed");
+  blob->ptr = out;
+  blob->len = total;
+  out_bytes = total;
+  return YCRDT_OK;
+}
+
+// The start of a call over n requests: no answer yet. True when the call ends here with rc: nothing
+// asked (the one-byte blob), or more than the device's 31-bit indices count (`too_many`).
+bool blob_start(size_t n, const char* too_many, ycrdt_out* blob, uint64_t* offs, int& rc) {
+  blob->ptr = nullptr;
+  blob->len = 0;
+  offs[0] = 0;
+  rc = YCRDT_OK;
+  if (n == 0) {
+    uint64_t none = 0;
+    rc = give_blob({}, blob, offs, none);
+  } else if (n >= 0x7FFFFFFFull) {
+    rc = fail(YCRDT_E_CAPACITY, too_many);
+  }
+  return n == 0 || rc != YCRDT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2851,18 +2918,11 @@ int ycrdt_docs_diff(ycrdt_engine* e, ycrdt_doc* const* docs, const ycrdt_buf* sv
   if (const int rc = check_docs(e, docs, n)) return rc;
   for (size_t i = 0; i < n; ++i)
     if (svs[i].len && !svs[i].ptr) return fail(YCRDT_E_ARG, "null state vector at " + std::to_string(i));
-  blob->ptr = nullptr;
-  blob->len = 0;
-  offs[0] = 0;
   ycrdt_sync_stats S{};
   S.walk_max = SYNC_WALK_MAX;
   if (st) *st = S;
-  if (n == 0) {
-    blob->ptr = (uint8_t*)malloc(1);
-    if (!blob->ptr) return fail(YCRDT_E_CAPACITY, "host allocation failed");
-    return YCRDT_OK;
-  }
-  if (n >= 0x7FFFFFFFull) return fail(YCRDT_E_CAPACITY, "too many pairs");
+  int rc0;
+  if (blob_start(n, "too many pairs", blob, offs, rc0)) return rc0;
   // the peers' state vectors: clients ascending, one run per pair (as ycrdt_diff_updates uploads them)
   std::vector<uint32_t> svk, svv;
   std::vector<uint32_t> sv_off(n + 1, 0);
@@ -2880,17 +2940,14 @@ int ycrdt_docs_diff(ycrdt_engine* e, ycrdt_doc* const* docs, const ycrdt_buf* sv
   HIPCHK(hipSetDevice(e->device));
   if (const int rc = flush_queued(e, docs, n)) return rc;
   // which path every pair takes
-  enum : uint8_t { K_SINGLE = 0, K_EMPTY, K_DEV };
   const bool off = env_off("YCRDT_SYNC");
   std::vector<uint8_t> kind(n, K_SINGLE);
   size_t ndev = 0;
   for (size_t i = 0; i < n; ++i) {
     const ycrdt_doc* d = docs[i];
-    if (off || d->ing.has_pending || d->ing.has_ds || e->compat == 135) continue;
-    if (!d->state_len) { kind[i] = K_EMPTY; continue; }
-    if (d->state_len >= (size_t(1) << 31) || (!marked(d) && d->state_len > SYNC_WALK_MAX)) continue;
-    kind[i] = K_DEV;
-    ++ndev;
+    kind[i] = doc_path(e, d, off);
+    if (kind[i] == K_DEV && !marked(d) && d->state_len > SYNC_WALK_MAX) kind[i] = K_SINGLE;
+    if (kind[i] == K_DEV) ++ndev;
   }
   std::vector<std::vector<uint8_t>> host(n);  // replies of the pairs the device path does not answer
   auto single = [&](size_t i) -> int {
@@ -3018,7 +3075,7 @@ int ycrdt_docs_diff(ycrdt_engine* e, ycrdt_doc* const* docs, const ycrdt_buf* sv
     A.np = np;
     A.nitems = (uint32_t)nitems;
     A.piece_max = PIECE_MAX;
-    A.dbg_bounds = getenv("YCRDT_DEBUG_BOUNDS") && getenv("YCRDT_DEBUG_BOUNDS")[0] == '1' ? 1u : 0u;
+    A.dbg_bounds = env_on("YCRDT_DEBUG_BOUNDS") ? 1u : 0u;
     mark(e, "sync_walk");
     launch_sync_walk(A.docs, (const SyncWalk*)(up + u_walk), nwk, A.ctr, A.dbg_bounds, s);
     mark(e, "sync_plan");
@@ -3086,34 +3143,14 @@ int ycrdt_docs_diff(ycrdt_engine* e, ycrdt_doc* const* docs, const ycrdt_buf* sv
         if (const int rc2 = single(dpair[k])) return rc2;
       }
   }
-  uint64_t total = 0;
-  {
-    size_t k = 0;
-    for (size_t i = 0; i < n; ++i) {
-      offs[i] = total;
-      if (k < dpair.size() && dpair[k] == i) {
-        if (kind[i] == K_DEV) total += doffs[k + 1] - doffs[k]; else total += host[i].size();
-        ++k;
-      } else {
-        total += host[i].size();
-      }
-    }
-    offs[n] = total;
+  // a device pair that kept its path: its slice of `dev`; every other pair: its host reply
+  std::vector<BlobPart> parts(n);
+  for (size_t i = 0, k = 0; i < n; ++i) {
+    const bool isdev = k < dpair.size() && dpair[k] == i;
+    parts[i] = isdev && kind[i] == K_DEV ? BlobPart{dev.data() + doffs[k], size_t(doffs[k + 1] - doffs[k])} : part_of(host[i]);
+    if (isdev) ++k;
   }
-  uint8_t* out = (uint8_t*)malloc(total ? total : 1);
-  if (!out) return fail(YCRDT_E_CAPACITY, "host allocation failed");
-  {
-    size_t k = 0;
-    for (size_t i = 0; i < n; ++i) {
-      const bool isdev = k < dpair.size() && dpair[k] == i;
-      if (isdev && kind[i] == K_DEV) memcpy(out + offs[i], dev.data() + doffs[k], doffs[k + 1] - doffs[k]);
-      else if (!host[i].empty()) memcpy(out + offs[i], host[i].data(), host[i].size());
-      if (isdev) ++k;
-    }
-  }
-  blob->ptr = out;
-  blob->len = total;
-  S.out_bytes = total;
+  if (const int rc = give_blob(parts, blob, offs, S.out_bytes)) return rc;
   if (st) *st = S;
   return YCRDT_OK;
 }
@@ -3148,9 +3185,10 @@ struct JsonExtra {           // what a caller other than json_pass needs beside 
   const std::vector<uint8_t>* up = nullptr;  // uploaded behind the request names
 };
 
-// The front half of one device pass, shared by ycrdt_docs_json and ycrdt_docs_read: the documents
-// dl merged as one multi-document batch, the view over it, the keys sorted into HostView::index's
-// order with the root names of `reqs` (sorted by rkey) checked, and every item sized bottom-up.
+// The front half of one device pass, shared by ycrdt_docs_json, ycrdt_docs_cache, ycrdt_docs_read and
+// ycrdt_docs_write: the documents dl merged as one multi-document batch, the view over it, the keys
+// sorted into HostView::index's order with the root names of `reqs` (sorted by rkey) checked, and
+// every item sized bottom-up.
 int json_front(ycrdt_engine* e, const std::vector<ycrdt_doc*>& dl, const std::vector<JsonReq>& reqs, const std::vector<uint8_t>& names,
                const JsonExtra& X, JsonFront& F) {
   auto refuse_all = [&]() { F.refused = true; return YCRDT_OK; };
@@ -3183,8 +3221,7 @@ int json_front(ycrdt_engine* e, const std::vector<ycrdt_doc*>& dl, const std::ve
   const uint32_t nreq = (uint32_t)reqs.size();
   // device workspace of the pass
   const uint64_t n = (uint64_t)ck + narr;
-  uint64_t at = 0;
-  auto lay = [&](uint64_t bytes) { const uint64_t o = at; at = (at + bytes + 63) & ~uint64_t(63); return o; };
+  Lay lay;
   const uint64_t o_rb = lay(8ull * (nreq + 1) + 4ull * nreq);  // offsets | flags: read back together
   const uint64_t o_roffs = o_rb, o_rflag = o_rb + 8ull * (nreq + 1);
   const uint64_t o_rsize = lay(4ull * (nreq + 1));
@@ -3193,11 +3230,11 @@ int json_front(ycrdt_engine* e, const std::vector<ycrdt_doc*>& dl, const std::ve
   const uint64_t o_scanc = lay(8 * (n + 1)), o_scant = lay(8ull * (narr + 1)), o_scanu = lay(4 * (n + 1));
   const uint64_t o_apos = lay(8 * n), o_cend = lay(8 * n), o_mbase = lay(8 * ck), o_abase = lay(8 * ck);
   const uint64_t o_extra = lay(X.ws_fixed + X.ws_per_item * (n + 1) + X.ws_per_key * ck);
-  const uint64_t ws_bytes = at + 64;
-  at = 0;
+  const uint64_t ws_bytes = lay.at + 64;
+  lay = Lay{};
   const uint64_t u_reqs = lay(sizeof(JsonReq) * (uint64_t)nreq), u_names = lay(names.size());
   const uint64_t u_extra = lay(X.up ? X.up->size() : 0);
-  const uint64_t up_bytes = at + 64;
+  const uint64_t up_bytes = lay.at + 64;
   uint8_t* W = take<uint8_t>(V, B_JSON, ws_bytes, ok);
   uint8_t* U = ok ? take<uint8_t>(V, B_JSONUP, up_bytes, ok) : nullptr;
   const size_t tmpb = prim_tmp_bytes(std::max<uint64_t>({n + 2, (uint64_t)nreq + 2, X.scan_n}), ck + 2);
@@ -3281,77 +3318,144 @@ int json_front(ycrdt_engine* e, const std::vector<ycrdt_doc*>& dl, const std::ve
   return YCRDT_OK;
 }
 
-// One device pass of ycrdt_docs_json: the front half over the documents dl, then the text of the
-// requests `ws` (indices into `wants`, their documents all in dl; pdoc maps a call document to its
-// index in dl). A request the device refuses — or every request, when the front half refuses the
-// batch — is left `refused` for the single path.
-int json_pass(ycrdt_engine* e, const std::vector<ycrdt_doc*>& dl, const std::vector<uint32_t>& pdoc,
-              std::vector<JsonWant>& wants, const std::vector<size_t>& ws, double& device_ms) {
-  auto refuse_all = [&]() { for (size_t k : ws) wants[k].refused = true; return YCRDT_OK; };
-  // the requests, sorted by (document, root name hash), and their names
-  const uint32_t nreq = (uint32_t)ws.size();
-  std::vector<size_t> order(ws);
-  std::vector<JsonReq> reqs(nreq);
-  std::vector<uint8_t> names;
-  auto rkey = [&](size_t k) {
-    return (1ull << 63) | ((uint64_t)pdoc[wants[k].doc] << 32) | (fnv_key((const uint8_t*)wants[k].name.data(), 0, (uint32_t)wants[k].name.size()) >> 1);  // as k_jsort_key hashes the root names
-  };
-  std::sort(order.begin(), order.end(), [&](size_t x, size_t y) {
-    const uint64_t a = rkey(x), c = rkey(y);
-    return a != c ? a < c : x < y;
+// ---- what the passes behind json_front share
+
+// The root key of a request: the document's index in its pass and the root name's hash, as
+// k_jsort_key keys the roots.
+uint64_t root_key(uint32_t pdoc, const char* name, size_t len) {
+  return (1ull << 63) | ((uint64_t)pdoc << 32) | (fnv_key((const uint8_t*)name, 0, (uint32_t)len) >> 1);
+}
+
+// The root requests of a pass. roots[r] is the root that want r of the pass names; the distinct
+// (document, root, kind) among them become `reqs`, sorted by root key as json_front asks (k_jindex
+// checks their names), the names pooled in `names`. root_of[r] is the request of want r.
+struct RootRef {
+  uint32_t pdoc;
+  const char* name;
+  size_t len;
+  uint32_t kind;
+};
+void root_requests(const std::vector<RootRef>& roots, std::vector<JsonReq>& reqs, std::vector<uint8_t>& names, std::vector<uint32_t>& root_of) {
+  const uint32_t nr = (uint32_t)roots.size();
+  std::vector<uint64_t> key(nr);
+  std::vector<uint32_t> order(nr);
+  for (uint32_t r = 0; r < nr; ++r) { key[r] = root_key(roots[r].pdoc, roots[r].name, roots[r].len); order[r] = r; }
+  std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
+    if (key[x] != key[y]) return key[x] < key[y];
+    const RootRef &a = roots[x], &c = roots[y];
+    const int by_name = memcmp(a.name, c.name, std::min(a.len, c.len));
+    return by_name ? by_name < 0 : a.len != c.len ? a.len < c.len : x < y;
   });
-  for (uint32_t r = 0; r < nreq; ++r) {
-    const JsonWant& q = wants[order[r]];
-    reqs[r] = JsonReq{rkey(order[r]), (uint32_t)names.size(), (uint32_t)q.name.size(), (uint32_t)q.kind, 0};
-    names.insert(names.end(), q.name.begin(), q.name.end());
-    if (names.size() >= 0xFFFFFFF0ull) return refuse_all();
+  root_of.assign(nr, 0);
+  for (uint32_t r : order) {
+    const RootRef& q = roots[r];
+    if (reqs.empty() || reqs.back().rkey != key[r] || reqs.back().kind != q.kind || reqs.back().name_len != q.len ||
+        memcmp(names.data() + reqs.back().name_pos, q.name, q.len) != 0) {
+      reqs.push_back(JsonReq{key[r], (uint32_t)names.size(), (uint32_t)q.len, q.kind, 0});
+      names.insert(names.end(), q.name, q.name + q.len);
+    }
+    root_of[r] = (uint32_t)reqs.size() - 1;
   }
-  JsonFront F;
-  if (const int rc = json_front(e, dl, reqs, names, JsonExtra{}, F)) return rc;
-  if (F.refused) return refuse_all();
-  JsonArgs& A = F.A;
-  Work& w = e->w;
-  auto& V = e->bufs;
-  bool ok = true;
+}
+
+// The size read-back of a pass, its one synchronise before the text: the pass's own block (rb.size()
+// bytes at dev_rb: offsets, the total last, and flags), the view's counters and key count, and the
+// 4-byte count `extra` of a call that has one. `refuse`: the merge or the view failed, the single
+// path answers every request of the pass.
+int size_readback(ycrdt_engine* e, const JsonFront& F, const uint8_t* dev_rb, std::vector<uint8_t>& rb, bool& refuse,
+                  uint32_t* extra = nullptr, const uint32_t* dev_extra = nullptr) {
   hipStream_t s = e->stream;
-  uint8_t* W = F.W;
-  uint8_t* tmp = F.tmp;
-  const size_t tmpb = F.tmpb;
-  const uint64_t o_rb = F.o_rb;
-  const size_t ck = A.ck;
-  launch_json_requests(A, s);
-  scan_u32_to_u64(tmp, tmpb, A.rsize, A.roffs, (uint64_t)nreq + 1, s);
-  // the one size read-back: offsets (the total is the last), request flags, the view's counters
-  std::vector<uint8_t> rb(8ull * (nreq + 1) + 4ull * nreq);
   Counters c;
   uint32_t nkeys = 0;
-  HIPCHK(hipMemcpyAsync(rb.data(), W + o_rb, rb.size(), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(&c, w.ctr, sizeof(Counters), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(rb.data(), dev_rb, rb.size(), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(&c, e->w.ctr, sizeof(Counters), hipMemcpyDeviceToHost, s));
   HIPCHK(hipMemcpyAsync(&nkeys, F.nkeys, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  if (extra) HIPCHK(hipMemcpyAsync(extra, dev_extra, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
-  if (c.err || nkeys > ck) return refuse_all();
-  const uint64_t* roffs = (const uint64_t*)rb.data();
-  const uint32_t* rflag = (const uint32_t*)(rb.data() + 8ull * (nreq + 1));
-  const uint64_t total = roffs[nreq];
-  uint8_t* outb = take<uint8_t>(V, B_PACK, total + 64, ok);
-  if (!ok) return fail(YCRDT_E_DEVICE, oom("fleet toJSON text"));
-  A.out = outb;
-  A.out_cap = total;
-  // offsets top-down, one level per launch, then sweep 3
-  launch_json_roots(A, s);
+  refuse = c.err || nkeys > F.A.ck;
+  return YCRDT_OK;
+}
+
+// The text tail of a pass, in three steps around the call's own write kernel. The buffer of its
+// `total` bytes (B_PACK) ...
+int text_buffer(ycrdt_engine* e, uint64_t total, const char* what, uint8_t*& outb) {
+  bool ok = true;
+  outb = take<uint8_t>(e->bufs, B_PACK, total + 64, ok);
+  return ok ? YCRDT_OK : fail(YCRDT_E_DEVICE, oom(what));
+}
+// ... toJSON's offsets top-down, one level per launch, and sweep 3 behind the seeds that kernel wrote ...
+void json_place_write(const JsonArgs& A, hipStream_t s) {
   for (uint32_t level = 0; level <= JSON_DEPTH_MAX; ++level) launch_json_place(A, s);
   launch_json_write(A, s);
+}
+// ... and the copy-out: ev1 behind the kernels, the `total` bytes at outb into `text` (allocated while
+// the kernels run; none when no byte was sized: the kernels were skipped) and a call's `extra` copy
+// in front of the one synchronise, the device time added.
+int text_out(ycrdt_engine* e, const uint8_t* outb, uint64_t total, std::vector<uint8_t>& text, double& device_ms,
+             void* extra = nullptr, const void* dev_extra = nullptr, size_t extra_bytes = 0) {
+  hipStream_t s = e->stream;
   HIPCHK(hipEventRecord(e->ev1, s));
-  std::vector<uint8_t> text(total);
-  if (const int rc2 = d2h_span(e, text.data(), outb, total)) return rc2;
+  text.resize(total);
+  if (total) {
+    if (extra) HIPCHK(hipMemcpyAsync(extra, dev_extra, extra_bytes, hipMemcpyDeviceToHost, s));
+    if (const int rc = d2h_span(e, text.data(), outb, total)) return rc;
+  }
   HIPCHK(hipStreamSynchronize(s));
   float ms = 0;
   hipEventElapsedTime(&ms, e->ev0, e->ev1);
   device_ms += ms;
-  for (uint32_t r = 0; r < nreq; ++r) {
-    JsonWant& q = wants[order[r]];
-    if (rflag[r] || roffs[r + 1] - roffs[r] < 2) { q.refused = true; continue; }
-    q.text.assign((const char*)text.data() + roffs[r], roffs[r + 1] - roffs[r]);
+  return YCRDT_OK;
+}
+
+// One device pass of ycrdt_docs_json: the front half over the documents dl (the call's device
+// documents from `first` on), then the text of the requests `ws` (indices into `wants`, their
+// documents all in dl). A request the device refuses — or every request, when the front half refuses
+// the batch — is left `refused` for the single path.
+int json_pass(ycrdt_engine* e, const std::vector<ycrdt_doc*>& dl, size_t first, std::vector<JsonWant>& wants,
+              const std::vector<size_t>& ws, double& device_ms) {
+  auto refuse_all = [&]() { for (size_t k : ws) wants[k].refused = true; return YCRDT_OK; };
+  const uint32_t nw = (uint32_t)ws.size();
+  std::vector<RootRef> roots(nw);
+  for (uint32_t r = 0; r < nw; ++r) {
+    const JsonWant& q = wants[ws[r]];
+    roots[r] = RootRef{uint32_t(q.doc - first), q.name.data(), q.name.size(), (uint32_t)q.kind};
+  }
+  std::vector<JsonReq> reqs;
+  std::vector<uint8_t> names;
+  std::vector<uint32_t> root_of;
+  root_requests(roots, reqs, names, root_of);
+  if (names.size() >= 0xFFFFFFF0ull) return refuse_all();
+  const uint32_t nreq = (uint32_t)reqs.size();
+  JsonFront F;
+  if (const int rc = json_front(e, dl, reqs, names, JsonExtra{}, F)) return rc;
+  if (F.refused) return refuse_all();
+  JsonArgs& A = F.A;
+  hipStream_t s = e->stream;
+  launch_json_requests(A, s);
+  scan_u32_to_u64(F.tmp, F.tmpb, A.rsize, A.roffs, (uint64_t)nreq + 1, s);
+  // the one size read-back: offsets (the total is the last), request flags, the view's counters
+  std::vector<uint8_t> rb(8ull * (nreq + 1) + 4ull * nreq);
+  bool refuse = false;
+  if (const int rc = size_readback(e, F, F.W + F.o_rb, rb, refuse)) return rc;
+  if (refuse) return refuse_all();
+  const uint64_t* roffs = (const uint64_t*)rb.data();
+  const uint32_t* rflag = (const uint32_t*)(rb.data() + 8ull * (nreq + 1));
+  const uint64_t total = roffs[nreq];
+  std::vector<uint8_t> text;
+  uint8_t* outb = nullptr;
+  if (total) {
+    if (const int rc = text_buffer(e, total, "fleet toJSON text", outb)) return rc;
+    A.out = outb;
+    A.out_cap = total;
+    launch_json_roots(A, s);
+    json_place_write(A, s);
+  }
+  if (const int rc = text_out(e, outb, total, text, device_ms)) return rc;
+  for (uint32_t r = 0; r < nw; ++r) {
+    JsonWant& q = wants[ws[r]];
+    const uint32_t x = root_of[r];
+    if (rflag[x] || roffs[x + 1] - roffs[x] < 2) { q.refused = true; continue; }
+    q.text.assign((const char*)text.data() + roffs[x], roffs[x + 1] - roffs[x]);
     q.done = true;
   }
   return YCRDT_OK;
@@ -3359,13 +3463,6 @@ int json_pass(ycrdt_engine* e, const std::vector<ycrdt_doc*>& dl, const std::vec
 
 }  // namespace
 
-constexpr uint64_t JSON_PASS_BYTES = uint64_t(1) << 31;  // resident state bytes merged per device pass (one 4 GiB window holds them)
-// (tests shrink a pass through YCRDT_DOCS_JSON_PASS_BYTES to run the several-pass path on a few documents)
-static uint64_t json_pass_bytes() {
-  const char* v = getenv("YCRDT_DOCS_JSON_PASS_BYTES");
-  const uint64_t x = v ? strtoull(v, nullptr, 10) : 0;
-  return x ? std::min(x, JSON_PASS_BYTES) : JSON_PASS_BYTES;
-}
 int ycrdt_docs_json(ycrdt_engine* e, ycrdt_doc* const* docs, const char* const* roots, const int* kinds, size_t n,
                     ycrdt_out* blob, uint64_t* offs, ycrdt_json_stats* st) {
   if (!e || !docs || !blob || !offs || (n && (!roots || !kinds))) return fail(YCRDT_E_ARG, "null arg");
@@ -3374,23 +3471,15 @@ int ycrdt_docs_json(ycrdt_engine* e, ycrdt_doc* const* docs, const char* const* 
     if (!roots[i]) return fail(YCRDT_E_ARG, "null root at " + std::to_string(i));
     if (kinds[i] < 0 || kinds[i] > 1) return fail(YCRDT_E_ARG, "kind outside {0, 1} at " + std::to_string(i));
   }
-  blob->ptr = nullptr;
-  blob->len = 0;
-  offs[0] = 0;
   ycrdt_json_stats S{};
   S.depth_max = JSON_DEPTH_MAX;
   S.name_max = JSON_NAME_MAX;
   if (st) *st = S;
-  if (n == 0) {
-    blob->ptr = (uint8_t*)malloc(1);
-    if (!blob->ptr) return fail(YCRDT_E_CAPACITY, "host allocation failed");
-    return YCRDT_OK;
-  }
-  if (n >= 0x7FFFFFFFull) return fail(YCRDT_E_CAPACITY, "too many requests");
+  int rc0;
+  if (blob_start(n, "too many requests", blob, offs, rc0)) return rc0;
   HIPCHK(hipSetDevice(e->device));
   if (const int rc = flush_queued(e, docs, n)) return rc;
   // which path every request takes; the device path's distinct documents and triples
-  enum : uint8_t { K_SINGLE = 0, K_EMPTY, K_DEV };
   const bool off = env_off("YCRDT_DOCS_JSON");
   std::vector<uint8_t> kind(n, K_SINGLE);
   std::vector<size_t> want_of(n, 0);
@@ -3399,21 +3488,17 @@ int ycrdt_docs_json(ycrdt_engine* e, ycrdt_doc* const* docs, const char* const* 
   std::vector<JsonWant> wants;
   std::unordered_map<std::string, size_t> wix;
   for (size_t i = 0; i < n; ++i) {
-    ycrdt_doc* d = docs[i];
-    if (off || d->ing.has_pending || d->ing.has_ds || e->compat == 135) continue;
-    if (!d->state_len) { kind[i] = K_EMPTY; continue; }
-    if (d->state_len >= JSON_PASS_BYTES) continue;
-    kind[i] = K_DEV;
-    auto it = dix.find(d);
-    if (it == dix.end()) { it = dix.emplace(d, (uint32_t)dlist.size()).first; dlist.push_back(d); }
-    std::string key((const char*)&it->second, 4);
+    kind[i] = doc_path(e, docs[i], off);
+    if (kind[i] != K_DEV) continue;
+    const uint32_t di = intern_doc(dix, dlist, docs[i]);
+    std::string key((const char*)&di, 4);
     key.push_back((char)kinds[i]);
     key += roots[i];
     auto wt = wix.find(key);
     if (wt == wix.end()) {
       wt = wix.emplace(key, wants.size()).first;
       JsonWant q;
-      q.doc = it->second;
+      q.doc = di;
       q.name = roots[i];
       q.kind = kinds[i];
       wants.push_back(std::move(q));
@@ -3422,32 +3507,21 @@ int ycrdt_docs_json(ycrdt_engine* e, ycrdt_doc* const* docs, const char* const* 
   }
   // device passes: documents in call order, as many as one window holds
   if (!wants.empty()) {
-    const uint64_t pass_bytes = json_pass_bytes();
+    // (tests shrink a pass through YCRDT_DOCS_JSON_PASS_BYTES to run the several-pass path on a few documents)
+    const std::vector<size_t> cut = doc_windows(dlist, pass_bytes(getenv("YCRDT_DOCS_JSON_PASS_BYTES"), JSON_PASS_BYTES));
     std::vector<std::vector<size_t>> by_doc(dlist.size());
     for (size_t k = 0; k < wants.size(); ++k) by_doc[wants[k].doc].push_back(k);
-    std::vector<uint32_t> pdoc(dlist.size(), 0);
-    size_t j = 0;
-    while (j < dlist.size()) {
-      std::vector<ycrdt_doc*> dl;
-      std::vector<size_t> ws;
-      uint64_t bytes = 0;
-      while (j < dlist.size() && (dl.empty() || bytes + dlist[j]->state_len + 64 <= pass_bytes)) {
-        bytes += (dlist[j]->state_len + 63) & ~size_t(63);
-        pdoc[j] = (uint32_t)dl.size();
-        dl.push_back(dlist[j]);
-        ws.insert(ws.end(), by_doc[j].begin(), by_doc[j].end());
-        ++j;
-      }
-      if (const int rc = json_pass(e, dl, pdoc, wants, ws, S.device_ms)) return rc;
+    for (size_t k = 0; k + 1 < cut.size(); ++k) {
+      const std::vector<ycrdt_doc*> dl(dlist.begin() + cut[k], dlist.begin() + cut[k + 1]);
+      if (const int rc = json_pass(e, dl, cut[k], wants, window_wants(by_doc, cut[k], cut[k + 1]), S.device_ms)) return rc;
     }
   }
   // everything else one by one (a repeated triple once)
   std::unordered_map<std::string, std::string> singles;
-  std::vector<const std::string*> text(n, nullptr);
-  static const std::string empty_map = "{}", empty_array = "[]";
+  std::vector<BlobPart> text(n);
   for (size_t i = 0; i < n; ++i) {
-    if (kind[i] == K_EMPTY) { text[i] = kinds[i] == 0 ? &empty_map : &empty_array; ++S.pairs_empty; continue; }
-    if (kind[i] == K_DEV && wants[want_of[i]].done) { text[i] = &wants[want_of[i]].text; ++S.pairs_device; continue; }
+    if (kind[i] == K_EMPTY) { text[i] = BlobPart{kinds[i] == 0 ? "{}" : "[]", 2}; ++S.pairs_empty; continue; }
+    if (kind[i] == K_DEV && wants[want_of[i]].done) { text[i] = part_of(wants[want_of[i]].text); ++S.pairs_device; continue; }
     const ycrdt_doc* d = docs[i];
     std::string key((const char*)&d, sizeof d);
     key.push_back((char)kinds[i]);
@@ -3459,18 +3533,10 @@ int ycrdt_docs_json(ycrdt_engine* e, ycrdt_doc* const* docs, const char* const* 
       it = singles.emplace(key, std::string((const char*)o.ptr, o.len)).first;
       ycrdt_free(&o);
     }
-    text[i] = &it->second;
+    text[i] = part_of(it->second);
     ++S.pairs_single;
   }
-  uint64_t total = 0;
-  for (size_t i = 0; i < n; ++i) { offs[i] = total; total += text[i]->size(); }
-  offs[n] = total;
-  uint8_t* out = (uint8_t*)malloc(total ? total : 1);
-  if (!out) return fail(YCRDT_E_CAPACITY, "host allocation failed");
-  for (size_t i = 0; i < n; ++i) memcpy(out + offs[i], text[i]->data(), text[i]->size());
-  blob->ptr = out;
-  blob->len = total;
-  S.out_bytes = total;
+  if (const int rc = give_blob(text, blob, offs, S.out_bytes)) return rc;
   if (st) *st = S;
   return YCRDT_OK;
 }
@@ -3486,17 +3552,16 @@ struct CacheWant {           // one distinct document of the device path
 
 // One device pass of ycrdt_docs_cache: the toJSON front half over the documents dl with one request
 // per document, (document, index, map), then the cache kernels and the toJSON placement and write.
-// ws[j] is the want of dl[j]. A document the device flags — or every document, when the front half
+// The want of dl[j] is first + j. A document the device flags — or every document, when the front half
 // refuses the batch — is left `refused` for the host composition.
 int cache_pass(ycrdt_engine* e, const std::vector<ycrdt_doc*>& dl, const std::string& index, std::vector<CacheWant>& wants,
-               const std::vector<size_t>& ws, uint64_t& roots, double& device_ms) {
-  auto refuse_all = [&]() { for (size_t k : ws) wants[k].refused = true; return YCRDT_OK; };
+               size_t first, uint64_t& roots, double& device_ms) {
   const uint32_t nd = (uint32_t)dl.size();
+  auto refuse_all = [&]() { for (uint32_t d = 0; d < nd; ++d) wants[first + d].refused = true; return YCRDT_OK; };
   // request d is document d: the root keys ascend with the document
   std::vector<JsonReq> reqs(nd);
   const std::vector<uint8_t> names(index.begin(), index.end());
-  const uint64_t ih = fnv_key((const uint8_t*)index.data(), 0, (uint32_t)index.size()) >> 1;  // as k_jsort_key hashes the root names
-  for (uint32_t d = 0; d < nd; ++d) reqs[d] = JsonReq{(1ull << 63) | ((uint64_t)d << 32) | ih, 0, (uint32_t)index.size(), 0, 0};
+  for (uint32_t d = 0; d < nd; ++d) reqs[d] = JsonReq{root_key(d, index.data(), index.size()), 0, (uint32_t)index.size(), 0, 0};
   JsonExtra X;
   X.ws_fixed = 16 * 64;
   X.ws_per_key = 4 * 6 + 8;  // live | lrank | mixed | smixed | msize | mkind, moffs
@@ -3504,12 +3569,9 @@ int cache_pass(ycrdt_engine* e, const std::vector<ycrdt_doc*>& dl, const std::st
   if (const int rc = json_front(e, dl, reqs, names, X, F)) return rc;
   if (F.refused) return refuse_all();
   JsonArgs& A = F.A;
-  auto& V = e->bufs;
-  bool ok = true;
   hipStream_t s = e->stream;
   const uint64_t ck = A.ck;
-  uint64_t at = 0;
-  auto lay = [&](uint64_t bytes) { const uint64_t o = at; at = (at + bytes + 63) & ~uint64_t(63); return o; };
+  Lay lay;
   const uint64_t o_roots = lay(4), o_live = lay(4 * (ck + 1)), o_lrank = lay(4 * (ck + 1)), o_mixed = lay(4 * (ck + 1));
   const uint64_t o_smixed = lay(4 * (ck + 1)), o_msize = lay(4 * (ck + 1)), o_moffs = lay(8 * (ck + 1)), o_mkind = lay(4 * ck);
   CacheArgs C{};
@@ -3532,50 +3594,32 @@ int cache_pass(ycrdt_engine* e, const std::vector<ycrdt_doc*>& dl, const std::st
   scan_u32_to_u64(F.tmp, F.tmpb, A.rsize, A.roffs, (uint64_t)nd + 1, s);
   // the one size read-back: offsets (the total is the last), document flags, members, the view's counters
   std::vector<uint8_t> rb(8ull * (nd + 1) + 4ull * nd);
-  Counters c;
-  uint32_t nkeys = 0, nroots = 0;
-  HIPCHK(hipMemcpyAsync(rb.data(), F.W + F.o_rb, rb.size(), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(&c, e->w.ctr, sizeof(Counters), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(&nkeys, F.nkeys, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(&nroots, C.roots, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  if (c.err || nkeys > ck) return refuse_all();
+  uint32_t nroots = 0;
+  bool refuse = false;
+  if (const int rc = size_readback(e, F, F.W + F.o_rb, rb, refuse, &nroots, C.roots)) return rc;
+  if (refuse) return refuse_all();
   const uint64_t* roffs = (const uint64_t*)rb.data();
   const uint32_t* rflag = (const uint32_t*)(rb.data() + 8ull * (nd + 1));
   const uint64_t total = roffs[nd];
-  std::vector<uint8_t> text(total);
+  std::vector<uint8_t> text;
+  uint8_t* outb = nullptr;
   if (total) {
-    uint8_t* outb = take<uint8_t>(V, B_PACK, total + 64, ok);
-    if (!ok) return fail(YCRDT_E_DEVICE, oom("fleet cache text"));
+    if (const int rc = text_buffer(e, total, "fleet cache text", outb)) return rc;
     C.j.out = A.out = outb;
     C.j.out_cap = A.out_cap = total;
     // braces, names and root positions, then offsets top-down and the members' bytes as toJSON does
     launch_cache_write(C, s);
-    for (uint32_t level = 0; level <= JSON_DEPTH_MAX; ++level) launch_json_place(A, s);
-    launch_json_write(A, s);
-    HIPCHK(hipEventRecord(e->ev1, s));
-    if (const int rc2 = d2h_span(e, text.data(), outb, total)) return rc2;
-  } else {
-    HIPCHK(hipEventRecord(e->ev1, s));
+    json_place_write(A, s);
   }
-  HIPCHK(hipStreamSynchronize(s));
-  float ms = 0;
-  hipEventElapsedTime(&ms, e->ev0, e->ev1);
-  device_ms += ms;
+  if (const int rc = text_out(e, outb, total, text, device_ms)) return rc;
   roots += nroots;
   for (uint32_t d = 0; d < nd; ++d) {
-    CacheWant& q = wants[ws[d]];
+    CacheWant& q = wants[first + d];
     if (rflag[d] || roffs[d + 1] - roffs[d] < 2) { q.refused = true; continue; }
     q.text.assign((const char*)text.data() + roffs[d], roffs[d + 1] - roffs[d]);
     q.done = true;
   }
   return YCRDT_OK;
-}
-
-uint64_t cache_pass_bytes() {  // (tests shrink a pass through YCRDT_DOCS_CACHE_PASS_BYTES, as YCRDT_DOCS_JSON_PASS_BYTES does)
-  const char* v = getenv("YCRDT_DOCS_CACHE_PASS_BYTES");
-  const uint64_t x = v ? strtoull(v, nullptr, 10) : 0;
-  return x ? std::min(x, JSON_PASS_BYTES) : JSON_PASS_BYTES;
 }
 
 }  // namespace
@@ -3585,63 +3629,38 @@ int ycrdt_docs_cache(ycrdt_engine* e, ycrdt_doc* const* docs, size_t n, const ch
   if (!e || !docs || !blob || !offs) return fail(YCRDT_E_ARG, "null arg");
   if (const int rc = check_docs(e, docs, n)) return rc;
   const std::string ix = index ? index : "ix";
-  blob->ptr = nullptr;
-  blob->len = 0;
-  offs[0] = 0;
   ycrdt_cache_stats S{};
   S.depth_max = JSON_DEPTH_MAX;
   S.name_max = JSON_NAME_MAX;
   if (st) *st = S;
-  if (n == 0) {
-    blob->ptr = (uint8_t*)malloc(1);
-    if (!blob->ptr) return fail(YCRDT_E_CAPACITY, "host allocation failed");
-    return YCRDT_OK;
-  }
-  if (n >= 0x7FFFFFFFull) return fail(YCRDT_E_CAPACITY, "too many documents");
+  int rc0;
+  if (blob_start(n, "too many documents", blob, offs, rc0)) return rc0;
   HIPCHK(hipSetDevice(e->device));
   if (const int rc = flush_queued(e, docs, n)) return rc;
   // which path every document takes; the device path's distinct documents
-  enum : uint8_t { K_SINGLE = 0, K_EMPTY, K_DEV };
   const bool off = env_off("YCRDT_DOCS_CACHE");
   std::vector<uint8_t> kind(n, K_SINGLE);
   std::vector<size_t> want_of(n, 0);
-  std::unordered_map<const ycrdt_doc*, size_t> dix;
+  std::unordered_map<const ycrdt_doc*, uint32_t> dix;
   std::vector<ycrdt_doc*> dlist;
   for (size_t i = 0; i < n; ++i) {
-    ycrdt_doc* d = docs[i];
-    if (off || d->ing.has_pending || d->ing.has_ds || e->compat == 135) continue;
-    if (!d->state_len) { kind[i] = K_EMPTY; continue; }
-    if (d->state_len >= JSON_PASS_BYTES) continue;
-    kind[i] = K_DEV;
-    auto it = dix.find(d);
-    if (it == dix.end()) { it = dix.emplace(d, dlist.size()).first; dlist.push_back(d); }
-    want_of[i] = it->second;
+    kind[i] = doc_path(e, docs[i], off);
+    if (kind[i] == K_DEV) want_of[i] = intern_doc(dix, dlist, docs[i]);
   }
   std::vector<CacheWant> wants(dlist.size());
-  // device passes: documents in call order, as many as one window holds
-  {
-    const uint64_t pass_bytes = cache_pass_bytes();
-    size_t j = 0;
-    while (j < dlist.size()) {
-      std::vector<ycrdt_doc*> dl;
-      std::vector<size_t> ws;
-      uint64_t bytes = 0;
-      while (j < dlist.size() && (dl.empty() || bytes + dlist[j]->state_len + 64 <= pass_bytes)) {
-        bytes += (dlist[j]->state_len + 63) & ~size_t(63);
-        dl.push_back(dlist[j]);
-        ws.push_back(j);
-        ++j;
-      }
-      if (const int rc = cache_pass(e, dl, ix, wants, ws, S.roots, S.device_ms)) return rc;
-    }
+  // device passes: documents in call order, as many as one window holds (document j is want j)
+  // (tests shrink a pass through YCRDT_DOCS_CACHE_PASS_BYTES, as YCRDT_DOCS_JSON_PASS_BYTES does)
+  const std::vector<size_t> cut = doc_windows(dlist, pass_bytes(getenv("YCRDT_DOCS_CACHE_PASS_BYTES"), JSON_PASS_BYTES));
+  for (size_t k = 0; k + 1 < cut.size(); ++k) {
+    const std::vector<ycrdt_doc*> dl(dlist.begin() + cut[k], dlist.begin() + cut[k + 1]);
+    if (const int rc = cache_pass(e, dl, ix, wants, cut[k], S.roots, S.device_ms)) return rc;
   }
   // everything else composed on the host, one document at a time (a repeated document once)
   std::unordered_map<const ycrdt_doc*, std::string> singles;
-  std::vector<const std::string*> text(n, nullptr);
-  static const std::string empty_object = "{}";
+  std::vector<BlobPart> text(n);
   for (size_t i = 0; i < n; ++i) {
-    if (kind[i] == K_EMPTY) { text[i] = &empty_object; ++S.docs_empty; continue; }
-    if (kind[i] == K_DEV && wants[want_of[i]].done) { text[i] = &wants[want_of[i]].text; ++S.docs_device; continue; }
+    if (kind[i] == K_EMPTY) { text[i] = BlobPart{"{}", 2}; ++S.docs_empty; continue; }
+    if (kind[i] == K_DEV && wants[want_of[i]].done) { text[i] = part_of(wants[want_of[i]].text); ++S.docs_device; continue; }
     auto it = singles.find(docs[i]);
     if (it == singles.end()) {
       if (const int rc = ensure_view(docs[i])) return rc;
@@ -3649,18 +3668,10 @@ int ycrdt_docs_cache(ycrdt_engine* e, ycrdt_doc* const* docs, size_t n, const ch
       view_cache_json(docs[i]->view, ix, j);
       it = singles.emplace(docs[i], std::move(j)).first;
     }
-    text[i] = &it->second;
+    text[i] = part_of(it->second);
     ++S.docs_single;
   }
-  uint64_t total = 0;
-  for (size_t i = 0; i < n; ++i) { offs[i] = total; total += text[i]->size(); }
-  offs[n] = total;
-  uint8_t* out = (uint8_t*)malloc(total ? total : 1);
-  if (!out) return fail(YCRDT_E_CAPACITY, "host allocation failed");
-  for (size_t i = 0; i < n; ++i) memcpy(out + offs[i], text[i]->data(), text[i]->size());
-  blob->ptr = out;
-  blob->len = total;
-  S.out_bytes = total;
+  if (const int rc = give_blob(text, blob, offs, S.out_bytes)) return rc;
   if (st) *st = S;
   return YCRDT_OK;
 }
@@ -3680,42 +3691,29 @@ struct ReadWant {            // one distinct read of the device path
   bool refused = false, done = false;
 };
 
-// One device pass: the toJSON front half over the documents dl, then the reads `ws` (indices into
-// `wants`, their documents all in dl) resolved, sized and written. A read the device refuses is left
-// `refused` for the single calls.
-int read_pass(ycrdt_engine* e, const std::vector<ycrdt_doc*>& dl, const std::vector<uint32_t>& pdoc, std::vector<ReadWant>& wants,
+// One device pass: the toJSON front half over the documents dl (the call's device documents from
+// `first` on), then the reads `ws` (indices into `wants`, their documents all in dl) resolved, sized
+// and written. A read the device refuses is left `refused` for the single calls.
+int read_pass(ycrdt_engine* e, const std::vector<ycrdt_doc*>& dl, size_t first, std::vector<ReadWant>& wants,
               const std::vector<size_t>& ws, double& device_ms) {
   auto refuse_all = [&]() { for (size_t k : ws) wants[k].refused = true; return YCRDT_OK; };
   const uint32_t nr = (uint32_t)ws.size();
-  // the distinct (document, root) of the reads, sorted as json_pass sorts its requests: k_jindex checks their names
-  auto rkey = [&](const ReadWant& q) {
-    return (1ull << 63) | ((uint64_t)pdoc[q.doc] << 32) | (fnv_key((const uint8_t*)q.root.data(), 0, (uint32_t)q.root.size()) >> 1);
-  };
-  std::vector<size_t> rorder(ws);
-  std::sort(rorder.begin(), rorder.end(), [&](size_t x, size_t y) {
-    const ReadWant &a = wants[x], &c = wants[y];
-    const uint64_t ka = rkey(a), kc = rkey(c);
-    return ka != kc ? ka < kc : a.root != c.root ? a.root < c.root : x < y;
-  });
+  // the distinct (document, root) of the reads
+  std::vector<RootRef> roots(nr);
+  for (uint32_t r = 0; r < nr; ++r) {
+    const ReadWant& q = wants[ws[r]];
+    roots[r] = RootRef{uint32_t(q.doc - first), q.root.data(), q.root.size(), 0};
+  }
   std::vector<JsonReq> reqs;
   std::vector<uint8_t> names;
-  std::unordered_map<size_t, uint32_t> root_of;  // want -> its root request
-  for (size_t k : rorder) {
-    const ReadWant& q = wants[k];
-    const uint64_t rk = rkey(q);
-    if (reqs.empty() || reqs.back().rkey != rk || reqs.back().name_len != q.root.size() ||
-        memcmp(names.data() + reqs.back().name_pos, q.root.data(), q.root.size()) != 0) {
-      reqs.push_back(JsonReq{rk, (uint32_t)names.size(), (uint32_t)q.root.size(), 0, 0});
-      names.insert(names.end(), q.root.begin(), q.root.end());
-    }
-    root_of[k] = (uint32_t)reqs.size() - 1;
-  }
+  std::vector<uint32_t> root_of;
+  root_requests(roots, reqs, names, root_of);
   std::vector<ReadReq> rr(nr);
   for (uint32_t r = 0; r < nr; ++r) {
     const ReadWant& q = wants[ws[r]];
     ReadReq x{};
     x.index = q.index;
-    x.root = root_of[ws[r]];
+    x.root = root_of[r];
     x.op = (uint32_t)q.op;
     x.pkey_pos = (uint32_t)names.size();
     x.pkey_len = q.nested ? (uint32_t)q.pkey.size() : READ_NONE;
@@ -3729,15 +3727,13 @@ int read_pass(ycrdt_engine* e, const std::vector<ycrdt_doc*>& dl, const std::vec
   std::vector<uint8_t> up(sizeof(ReadReq) * (size_t)nr);
   memcpy(up.data(), rr.data(), up.size());
   // the pass's own workspace: | offsets | counts | states | flags | (read back together) and the rest
-  uint64_t at = 0;
-  auto lay = [&](uint64_t bytes) { const uint64_t o = at; at = (at + bytes + 63) & ~uint64_t(63); return o; };
+  Lay lay;
   const uint64_t rb_bytes = 8ull * (nr + 1) + 8ull * nr + 4ull * nr + 4ull * nr;
   const uint64_t o_rb = lay(rb_bytes);
   const uint64_t o_voffs = o_rb, o_counts = o_voffs + 8ull * (nr + 1), o_states = o_counts + 8ull * nr, o_flags = o_states + 4ull * nr;
   const uint64_t o_item = lay(4ull * nr), o_elem = lay(4ull * nr), o_vsize = lay(4ull * (nr + 1)), o_oflag = lay(4ull * nr);
-  const uint64_t fixed = at;
   JsonExtra X;
-  X.ws_fixed = fixed + 4 * 64;  // (the per-key and per-item arrays below start on 64-byte lines)
+  X.ws_fixed = lay.at + 4 * 64;  // (the per-key and per-item arrays below start on 64-byte lines)
   X.ws_per_item = 12;           // vis | scan_v
   X.ws_per_key = 8;             // own_m | own_a
   X.scan_n = (uint64_t)nr + 2;
@@ -3746,8 +3742,6 @@ int read_pass(ycrdt_engine* e, const std::vector<ycrdt_doc*>& dl, const std::vec
   if (const int rc = json_front(e, dl, reqs, names, X, F)) return rc;
   if (F.refused) return refuse_all();
   JsonArgs& A = F.A;
-  auto& V = e->bufs;
-  bool ok = true;
   hipStream_t s = e->stream;
   const uint64_t n = F.n, ck = A.ck;
   const uint64_t o_ownm = lay(4 * ck), o_owna = lay(4 * ck), o_vis = lay(4 * (n + 1)), o_scanv = lay(8 * (n + 1));
@@ -3778,39 +3772,27 @@ int read_pass(ycrdt_engine* e, const std::vector<ycrdt_doc*>& dl, const std::vec
   scan_u32_to_u64(F.tmp, F.tmpb, R.vsize, R.voffs, (uint64_t)nr + 1, s);
   // the one size read-back: offsets (the total is the last), counts, states, flags, the view's counters
   std::vector<uint8_t> rb(rb_bytes);
-  Counters c;
-  uint32_t nkeys = 0;
-  HIPCHK(hipMemcpyAsync(rb.data(), X0 + o_rb, rb.size(), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(&c, e->w.ctr, sizeof(Counters), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(&nkeys, F.nkeys, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  if (c.err || nkeys > ck) return refuse_all();
+  bool refuse = false;
+  if (const int rc = size_readback(e, F, X0 + o_rb, rb, refuse)) return rc;
+  if (refuse) return refuse_all();
   const uint64_t* voffs = (const uint64_t*)rb.data();
   const uint64_t* counts = (const uint64_t*)(rb.data() + 8ull * (nr + 1));
   const int32_t* states = (const int32_t*)(rb.data() + 8ull * (nr + 1) + 8ull * nr);
   const uint32_t* flags = (const uint32_t*)(rb.data() + 8ull * (nr + 1) + 8ull * nr + 4ull * nr);
   const uint64_t total = voffs[nr];
-  std::vector<uint8_t> text(total);
+  std::vector<uint8_t> text;
   std::vector<uint32_t> oflag(nr, 0);
+  uint8_t* outb = nullptr;
   if (total) {
-    uint8_t* outb = take<uint8_t>(V, B_PACK, total + 64, ok);
-    if (!ok) return fail(YCRDT_E_DEVICE, oom("fleet read text"));
+    if (const int rc = text_buffer(e, total, "fleet read text", outb)) return rc;
     R.j.out = A.out = outb;
     R.j.out_cap = A.out_cap = total;
     // scalar values and the seeds of nested types, then offsets top-down and the members' bytes
     launch_read_write(R, s);
-    for (uint32_t level = 0; level <= JSON_DEPTH_MAX; ++level) launch_json_place(A, s);
-    launch_json_write(A, s);
-    HIPCHK(hipEventRecord(e->ev1, s));
-    HIPCHK(hipMemcpyAsync(oflag.data(), A.oflag, 4ull * nr, hipMemcpyDeviceToHost, s));
-    if (const int rc2 = d2h_span(e, text.data(), outb, total)) return rc2;
-  } else {
-    HIPCHK(hipEventRecord(e->ev1, s));
+    json_place_write(A, s);
   }
-  HIPCHK(hipStreamSynchronize(s));
-  float ms = 0;
-  hipEventElapsedTime(&ms, e->ev0, e->ev1);
-  device_ms += ms;
+  // (the flags of the nested values ride between ev1 and the text)
+  if (const int rc = text_out(e, outb, total, text, device_ms, oflag.data(), A.oflag, 4ull * nr)) return rc;
   for (uint32_t r = 0; r < nr; ++r) {
     ReadWant& q = wants[ws[r]];
     if (flags[r] || oflag[r]) { q.refused = true; continue; }
@@ -3820,12 +3802,6 @@ int read_pass(ycrdt_engine* e, const std::vector<ycrdt_doc*>& dl, const std::vec
     q.done = true;
   }
   return YCRDT_OK;
-}
-
-uint64_t read_pass_bytes() {  // (tests shrink a pass through YCRDT_DOCS_READ_PASS_BYTES, as YCRDT_DOCS_JSON_PASS_BYTES does)
-  const char* v = getenv("YCRDT_DOCS_READ_PASS_BYTES");
-  const uint64_t x = v ? strtoull(v, nullptr, 10) : 0;
-  return x ? std::min(x, JSON_PASS_BYTES) : JSON_PASS_BYTES;
 }
 
 struct ReadAnswer {
@@ -3869,19 +3845,12 @@ int ycrdt_docs_read(ycrdt_engine* e, const ycrdt_read* reads, size_t n, ycrdt_ou
     if (q.op < YCRDT_READ_MAP_GET || q.op > YCRDT_READ_ARRAY_LENGTH) return fail(YCRDT_E_ARG, "op outside the four at " + std::to_string(i));
     if (q.op == YCRDT_READ_MAP_GET && !q.key) return fail(YCRDT_E_ARG, "null key at " + std::to_string(i));
   }
-  blob->ptr = nullptr;
-  blob->len = 0;
-  offs[0] = 0;
   ycrdt_read_stats S{};
   S.depth_max = JSON_DEPTH_MAX;
   S.name_max = JSON_NAME_MAX;
   if (st) *st = S;
-  if (n == 0) {
-    blob->ptr = (uint8_t*)malloc(1);
-    if (!blob->ptr) return fail(YCRDT_E_CAPACITY, "host allocation failed");
-    return YCRDT_OK;
-  }
-  if (n >= 0x7FFFFFFFull) return fail(YCRDT_E_CAPACITY, "too many reads");
+  int rc0;
+  if (blob_start(n, "too many reads", blob, offs, rc0)) return rc0;
   HIPCHK(hipSetDevice(e->device));
   {
     std::vector<ycrdt_doc*> docs(n);
@@ -3889,7 +3858,6 @@ int ycrdt_docs_read(ycrdt_engine* e, const ycrdt_read* reads, size_t n, ycrdt_ou
     if (const int rc = flush_queued(e, docs.data(), n)) return rc;
   }
   // which path every read takes; the device path's distinct documents and reads
-  enum : uint8_t { K_SINGLE = 0, K_EMPTY, K_DEV };
   const bool off = env_off("YCRDT_DOCS_READ");
   std::vector<uint8_t> kind(n, K_SINGLE);
   std::vector<size_t> want_of(n, 0);
@@ -3912,21 +3880,18 @@ int ycrdt_docs_read(ycrdt_engine* e, const ycrdt_read* reads, size_t n, ycrdt_ou
   };
   for (size_t i = 0; i < n; ++i) {
     const ycrdt_read& q = reads[i];
-    ycrdt_doc* d = q.doc;
-    if (off || d->ing.has_pending || d->ing.has_ds || e->compat == 135) continue;
-    if (!d->state_len) { kind[i] = K_EMPTY; continue; }
-    if (d->state_len >= JSON_PASS_BYTES) continue;
+    const DocPath path = doc_path(e, q.doc, off);
+    if (path != K_DEV) { kind[i] = path; continue; }
     if (q.parent_key && strlen(q.parent_key) > JSON_NAME_MAX) continue;
     if (q.op == YCRDT_READ_MAP_GET && strlen(q.key) > JSON_NAME_MAX) continue;
     kind[i] = K_DEV;
-    auto it = dix.find(d);
-    if (it == dix.end()) { it = dix.emplace(d, (uint32_t)dlist.size()).first; dlist.push_back(d); }
-    const std::string key = read_key(&it->second, 4, q);
+    const uint32_t di = intern_doc(dix, dlist, q.doc);
+    const std::string key = read_key(&di, 4, q);
     auto wt = wix.find(key);
     if (wt == wix.end()) {
       wt = wix.emplace(key, wants.size()).first;
       ReadWant w;
-      w.doc = it->second;
+      w.doc = di;
       w.op = q.op;
       w.nested = q.parent_key != nullptr;
       w.root = q.root;
@@ -3939,34 +3904,22 @@ int ycrdt_docs_read(ycrdt_engine* e, const ycrdt_read* reads, size_t n, ycrdt_ou
   }
   // device passes: documents in call order, as many as one window holds
   if (!wants.empty()) {
-    const uint64_t pass_bytes = read_pass_bytes();
+    // (tests shrink a pass through YCRDT_DOCS_READ_PASS_BYTES, as YCRDT_DOCS_JSON_PASS_BYTES does)
+    const std::vector<size_t> cut = doc_windows(dlist, pass_bytes(getenv("YCRDT_DOCS_READ_PASS_BYTES"), JSON_PASS_BYTES));
     std::vector<std::vector<size_t>> by_doc(dlist.size());
     for (size_t k = 0; k < wants.size(); ++k) by_doc[wants[k].doc].push_back(k);
-    std::vector<uint32_t> pdoc(dlist.size(), 0);
-    size_t j = 0;
-    while (j < dlist.size()) {
-      std::vector<ycrdt_doc*> dl;
-      std::vector<size_t> ws;
-      uint64_t bytes = 0;
-      while (j < dlist.size() && (dl.empty() || bytes + dlist[j]->state_len + 64 <= pass_bytes)) {
-        bytes += (dlist[j]->state_len + 63) & ~size_t(63);
-        pdoc[j] = (uint32_t)dl.size();
-        dl.push_back(dlist[j]);
-        ws.insert(ws.end(), by_doc[j].begin(), by_doc[j].end());
-        ++j;
-      }
-      if (const int rc = read_pass(e, dl, pdoc, wants, ws, S.device_ms)) return rc;
+    for (size_t k = 0; k + 1 < cut.size(); ++k) {
+      const std::vector<ycrdt_doc*> dl(dlist.begin() + cut[k], dlist.begin() + cut[k + 1]);
+      if (const int rc = read_pass(e, dl, cut[k], wants, window_wants(by_doc, cut[k], cut[k + 1]), S.device_ms)) return rc;
     }
   }
   // everything else one by one (a repeated read once)
   std::unordered_map<std::string, ReadAnswer> singles;
-  std::vector<const std::string*> text(n, nullptr);
-  static const std::string none;
+  std::vector<BlobPart> text(n, BlobPart{nullptr, 0});
   for (size_t i = 0; i < n; ++i) {
     const ycrdt_read& q = reads[i];
     const bool sized = q.op == YCRDT_READ_MAP_SIZE || q.op == YCRDT_READ_ARRAY_LENGTH;
     if (kind[i] == K_EMPTY) {
-      text[i] = &none;
       states[i] = sized ? 1 : 0;
       counts[i] = 0;
       ++S.reads_empty;
@@ -3974,7 +3927,7 @@ int ycrdt_docs_read(ycrdt_engine* e, const ycrdt_read* reads, size_t n, ycrdt_ou
     }
     if (kind[i] == K_DEV && wants[want_of[i]].done) {
       const ReadWant& w = wants[want_of[i]];
-      text[i] = &w.text;
+      text[i] = part_of(w.text);
       states[i] = w.state;
       counts[i] = w.count;
       ++S.reads_device;
@@ -3987,20 +3940,12 @@ int ycrdt_docs_read(ycrdt_engine* e, const ycrdt_read* reads, size_t n, ycrdt_ou
       if (const int rc = read_single(q, a)) return rc;
       it = singles.emplace(key, std::move(a)).first;
     }
-    text[i] = &it->second.text;
+    text[i] = part_of(it->second.text);
     states[i] = it->second.state;
     counts[i] = it->second.count;
     ++S.reads_single;
   }
-  uint64_t total = 0;
-  for (size_t i = 0; i < n; ++i) { offs[i] = total; total += text[i]->size(); }
-  offs[n] = total;
-  uint8_t* out = (uint8_t*)malloc(total ? total : 1);
-  if (!out) return fail(YCRDT_E_CAPACITY, "host allocation failed");
-  for (size_t i = 0; i < n; ++i) memcpy(out + offs[i], text[i]->data(), text[i]->size());
-  blob->ptr = out;
-  blob->len = total;
-  S.out_bytes = total;
+  if (const int rc = give_blob(text, blob, offs, S.out_bytes)) return rc;
   if (st) *st = S;
   return YCRDT_OK;
 }
@@ -4803,38 +4748,24 @@ struct WriteWant {           // one op of the device path
 
 const char* str_or_empty(const char* s) { return s ? s : ""; }
 
-// One device pass: the toJSON front half over the documents dl, the visible scan of the reads, then
-// the ops `ws` (indices into `wants`, their documents all in dl) planned, sized and written. An op
-// the device refuses is left `refused`: its document goes through the single calls.
-int write_pass(ycrdt_engine* e, const std::vector<ycrdt_doc*>& dl, const std::vector<uint32_t>& pdoc, const ycrdt_write* ops,
+// One device pass: the toJSON front half over the documents dl (the call's device documents from
+// `first` on), the visible scan of the reads, then the ops `ws` (indices into `wants`, their
+// documents all in dl) planned, sized and written. An op the device refuses is left `refused`: its
+// document goes through the single calls.
+int write_pass(ycrdt_engine* e, const std::vector<ycrdt_doc*>& dl, size_t first, const ycrdt_write* ops,
                std::vector<WriteWant>& wants, const std::vector<size_t>& ws, double& device_ms) {
   auto refuse_all = [&]() { for (size_t k : ws) wants[k].refused = true; return YCRDT_OK; };
   const uint32_t nr = (uint32_t)ws.size();
-  // the distinct (document, root) of the ops, sorted as json_pass sorts its requests: k_jindex checks their names
-  auto rkey = [&](size_t k) {
-    const char* root = ops[wants[k].op].root;
-    return (1ull << 63) | ((uint64_t)pdoc[wants[k].doc] << 32) | (fnv_key((const uint8_t*)root, 0, (uint32_t)strlen(root)) >> 1);
-  };
-  std::vector<size_t> rorder(ws);
-  std::sort(rorder.begin(), rorder.end(), [&](size_t x, size_t y) {
-    const uint64_t ka = rkey(x), kc = rkey(y);
-    const int c = strcmp(ops[wants[x].op].root, ops[wants[y].op].root);
-    return ka != kc ? ka < kc : c != 0 ? c < 0 : x < y;
-  });
+  // the distinct (document, root) of the ops
+  std::vector<RootRef> roots(nr);
+  for (uint32_t r = 0; r < nr; ++r) {
+    const WriteWant& w = wants[ws[r]];
+    roots[r] = RootRef{uint32_t(w.doc - first), ops[w.op].root, strlen(ops[w.op].root), 0};
+  }
   std::vector<JsonReq> reqs;
   std::vector<uint8_t> names;
-  std::unordered_map<size_t, uint32_t> root_of;  // want -> its root request
-  for (size_t k : rorder) {
-    const char* root = ops[wants[k].op].root;
-    const size_t len = strlen(root);
-    const uint64_t rk = rkey(k);
-    if (reqs.empty() || reqs.back().rkey != rk || reqs.back().name_len != len ||
-        memcmp(names.data() + reqs.back().name_pos, root, len) != 0) {
-      reqs.push_back(JsonReq{rk, (uint32_t)names.size(), (uint32_t)len, 0, 0});
-      names.insert(names.end(), root, root + len);
-    }
-    root_of[k] = (uint32_t)reqs.size() - 1;
-  }
+  std::vector<uint32_t> root_of;
+  root_requests(roots, reqs, names, root_of);
   // the ops, their names and their values' bytes behind the root names
   std::vector<WriteReq> wr(nr);
   auto pool = [&](const void* p, size_t len) {
@@ -4850,13 +4781,13 @@ int write_pass(ycrdt_engine* e, const std::vector<ycrdt_doc*>& dl, const std::ve
     if (names.size() + (q.parent_key ? strlen(q.parent_key) : 0) + (map_op ? strlen(q.key) : 0) + (values ? q.any_len : 0) >= 0xFFFFFFF0ull)
       return refuse_all();
     WriteReq x{};
-    x.root = root_of[ws[r]];
+    x.root = root_of[r];
     x.op = (uint32_t)q.op;
     x.pkey_len = q.parent_key ? (uint32_t)strlen(q.parent_key) : READ_NONE;
     x.pkey_pos = pool(q.parent_key, q.parent_key ? x.pkey_len : 0);
     x.key_len = map_op ? (uint32_t)strlen(q.key) : 0;
     x.key_pos = pool(q.key, x.key_len);
-    x.client = dl[pdoc[w.doc]]->client_id;
+    x.client = dl[w.doc - first]->client_id;
     x.clock = w.clock;
     x.index = q.index;
     x.length = q.length;
@@ -4868,15 +4799,13 @@ int write_pass(ycrdt_engine* e, const std::vector<ycrdt_doc*>& dl, const std::ve
   std::vector<uint8_t> up(sizeof(WriteReq) * (size_t)nr);
   memcpy(up.data(), wr.data(), up.size());
   // the pass's own workspace: | offsets | reasons | flags | (read back together) and the rest
-  uint64_t at = 0;
-  auto lay = [&](uint64_t bytes) { const uint64_t o = at; at = (at + bytes + 63) & ~uint64_t(63); return o; };
+  Lay lay;
   const uint64_t rb_bytes = 8ull * (nr + 1) + 4ull * nr + 4ull * nr;
   const uint64_t o_rb = lay(rb_bytes);
   const uint64_t o_offs = o_rb, o_why = o_offs + 8ull * (nr + 1), o_flags = o_why + 4ull * nr;
   const uint64_t o_size = lay(4ull * (nr + 1)), o_plan = lay(sizeof(WritePlan) * (uint64_t)nr);
-  const uint64_t fixed = at;
   JsonExtra X;
-  X.ws_fixed = fixed + 4 * 64;  // (the per-item arrays below start on 64-byte lines)
+  X.ws_fixed = lay.at + 4 * 64;  // (the per-item arrays below start on 64-byte lines)
   X.ws_per_item = 12;           // vis | scan_v
   X.scan_n = (uint64_t)nr + 2;
   X.up = &up;
@@ -4884,8 +4813,6 @@ int write_pass(ycrdt_engine* e, const std::vector<ycrdt_doc*>& dl, const std::ve
   if (const int rc = json_front(e, dl, reqs, names, X, F)) return rc;
   if (F.refused) return refuse_all();
   JsonArgs& A = F.A;
-  auto& V = e->bufs;
-  bool ok = true;
   hipStream_t s = e->stream;
   const uint64_t n = F.n;
   const uint64_t o_vis = lay(4 * (n + 1)), o_scanv = lay(8 * (n + 1));
@@ -4911,33 +4838,22 @@ int write_pass(ycrdt_engine* e, const std::vector<ycrdt_doc*>& dl, const std::ve
   scan_u32_to_u64(F.tmp, F.tmpb, Wa.size, Wa.offs, (uint64_t)nr + 1, s);
   // the first read-back: offsets (the total is the last), reasons, flags, the view's counters
   std::vector<uint8_t> rb(rb_bytes);
-  Counters c;
-  uint32_t nkeys = 0;
-  HIPCHK(hipMemcpyAsync(rb.data(), X0 + o_rb, rb.size(), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(&c, e->w.ctr, sizeof(Counters), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(&nkeys, F.nkeys, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  if (c.err || nkeys > A.ck) return refuse_all();
+  bool refuse = false;
+  if (const int rc = size_readback(e, F, X0 + o_rb, rb, refuse)) return rc;
+  if (refuse) return refuse_all();
   const uint64_t* offs = (const uint64_t*)rb.data();
   const int32_t* why = (const int32_t*)(rb.data() + 8ull * (nr + 1));
   const uint32_t* flags = (const uint32_t*)(rb.data() + 8ull * (nr + 1) + 4ull * nr);
   const uint64_t total = offs[nr];
-  std::vector<uint8_t> text(total);
-  if (total) {  // the second read-back: the updates
-    uint8_t* outb = take<uint8_t>(V, B_PACK, total + 64, ok);
-    if (!ok) return fail(YCRDT_E_DEVICE, oom("fleet write updates"));
+  std::vector<uint8_t> text;
+  uint8_t* outb = nullptr;
+  if (total) {
+    if (const int rc = text_buffer(e, total, "fleet write updates", outb)) return rc;
     Wa.j.out = outb;
     Wa.j.out_cap = total;
     launch_write_write(Wa, s);
-    HIPCHK(hipEventRecord(e->ev1, s));
-    if (const int rc2 = d2h_span(e, text.data(), outb, total)) return rc2;
-  } else {
-    HIPCHK(hipEventRecord(e->ev1, s));
   }
-  HIPCHK(hipStreamSynchronize(s));
-  float ms = 0;
-  hipEventElapsedTime(&ms, e->ev0, e->ev1);
-  device_ms += ms;
+  if (const int rc = text_out(e, outb, total, text, device_ms)) return rc;  // the second read-back: the updates
   for (uint32_t r = 0; r < nr; ++r) {
     WriteWant& w = wants[ws[r]];
     if (flags[r] || offs[r + 1] < offs[r] || offs[r + 1] > total) { w.refused = true; continue; }
@@ -4945,12 +4861,6 @@ int write_pass(ycrdt_engine* e, const std::vector<ycrdt_doc*>& dl, const std::ve
     w.update.assign(text.data() + offs[r], text.data() + offs[r + 1]);
   }
   return YCRDT_OK;
-}
-
-uint64_t write_pass_bytes() {  // (tests shrink a pass through YCRDT_DOCS_WRITE_PASS_BYTES, as YCRDT_DOCS_READ_PASS_BYTES does)
-  const char* v = getenv("YCRDT_DOCS_WRITE_PASS_BYTES");
-  const uint64_t x = v ? strtoull(v, nullptr, 10) : 0;
-  return x ? std::min(x, JSON_PASS_BYTES) : JSON_PASS_BYTES;
 }
 
 // op q through the single call of its kind
@@ -5020,19 +4930,12 @@ int ycrdt_docs_write(ycrdt_engine* e, const ycrdt_write* ops, size_t n, ycrdt_ou
     if (!q.root) return fail(YCRDT_E_ARG, "null root at " + std::to_string(i));
     if (q.op < YCRDT_WRITE_MAP_SET || q.op > YCRDT_WRITE_ARRAY_DELETE) return fail(YCRDT_E_ARG, "op outside the six at " + std::to_string(i));
   }
-  blob->ptr = nullptr;
-  blob->len = 0;
-  offs[0] = 0;
   ycrdt_write_stats S{};
   S.ranges_max = WRITE_RANGES_MAX;
   S.name_max = JSON_NAME_MAX;
   if (st) *st = S;
-  if (n == 0) {
-    blob->ptr = (uint8_t*)malloc(1);
-    if (!blob->ptr) return fail(YCRDT_E_CAPACITY, "host allocation failed");
-    return YCRDT_OK;
-  }
-  if (n >= 0x7FFFFFFFull) return fail(YCRDT_E_CAPACITY, "too many ops");
+  int rc0;
+  if (blob_start(n, "too many ops", blob, offs, rc0)) return rc0;
   HIPCHK(hipSetDevice(e->device));
   {
     std::vector<ycrdt_doc*> docs(n);
@@ -5040,7 +4943,6 @@ int ycrdt_docs_write(ycrdt_engine* e, const ycrdt_write* ops, size_t n, ycrdt_ou
     if (const int rc = flush_queued(e, docs.data(), n)) return rc;
   }
   // the call's documents and the path each takes: all ops of one document take the same one
-  enum : uint8_t { K_SINGLE = 0, K_EMPTY, K_DEV };
   const bool off = env_off("YCRDT_DOCS_WRITE");
   std::vector<uint8_t> bad(n, 0);
   for (size_t i = 0; i < n; ++i) bad[i] = write_args_bad(ops[i]) ? 1 : 0;
@@ -5049,10 +4951,9 @@ int ycrdt_docs_write(ycrdt_engine* e, const ycrdt_write* ops, size_t n, ycrdt_ou
   std::vector<std::vector<size_t>> cops;
   std::vector<uint32_t> cdoc_of(n, 0);
   for (size_t i = 0; i < n; ++i) {
-    auto it = cix.find(ops[i].doc);
-    if (it == cix.end()) { it = cix.emplace(ops[i].doc, (uint32_t)cdocs.size()).first; cdocs.push_back(ops[i].doc); cops.emplace_back(); }
-    cops[it->second].push_back(i);
-    cdoc_of[i] = it->second;
+    cdoc_of[i] = intern_doc(cix, cdocs, ops[i].doc);
+    if (cops.size() < cdocs.size()) cops.emplace_back();
+    cops[cdoc_of[i]].push_back(i);
   }
   std::vector<uint8_t> kind(cdocs.size(), K_SINGLE);
   std::vector<ycrdt_doc*> dlist;            // the device path's documents, in call order
@@ -5061,9 +4962,8 @@ int ycrdt_docs_write(ycrdt_engine* e, const ycrdt_write* ops, size_t n, ycrdt_ou
   std::vector<size_t> want_of(n, SIZE_MAX);
   for (size_t c = 0; c < cdocs.size(); ++c) {
     ycrdt_doc* d = cdocs[c];
-    if (off || d->ing.has_pending || d->ing.has_ds || e->compat == 135) continue;
-    if (!d->state_len) { kind[c] = K_EMPTY; continue; }
-    if (d->state_len >= JSON_PASS_BYTES) continue;
+    const DocPath path = doc_path(e, d, off);
+    if (path != K_DEV) { kind[c] = path; continue; }
     bool fits = true;
     for (size_t i : cops[c]) {
       if (bad[i]) continue;
@@ -5092,22 +4992,13 @@ int ycrdt_docs_write(ycrdt_engine* e, const ycrdt_write* ops, size_t n, ycrdt_ou
   }
   // device passes: documents in call order, as many as one window holds
   if (!wants.empty()) {
-    const uint64_t pass_bytes = write_pass_bytes();
-    std::vector<uint32_t> pdoc(dlist.size(), 0);
-    size_t j = 0;
-    while (j < dlist.size()) {
-      std::vector<ycrdt_doc*> dl;
-      std::vector<size_t> ws;
-      uint64_t bytes = 0;
-      while (j < dlist.size() && (dl.empty() || bytes + dlist[j]->state_len + 64 <= pass_bytes)) {
-        bytes += (dlist[j]->state_len + 63) & ~size_t(63);
-        pdoc[j] = (uint32_t)dl.size();
-        dl.push_back(dlist[j]);
-        ws.insert(ws.end(), by_doc[j].begin(), by_doc[j].end());
-        ++j;
-      }
-      if (ws.empty()) continue;
-      if (const int rc = write_pass(e, dl, pdoc, ops, wants, ws, S.device_ms)) return rc;
+    // (tests shrink a pass through YCRDT_DOCS_WRITE_PASS_BYTES, as YCRDT_DOCS_READ_PASS_BYTES does)
+    const std::vector<size_t> cut = doc_windows(dlist, pass_bytes(getenv("YCRDT_DOCS_WRITE_PASS_BYTES"), JSON_PASS_BYTES));
+    for (size_t k = 0; k + 1 < cut.size(); ++k) {
+      const std::vector<ycrdt_doc*> dl(dlist.begin() + cut[k], dlist.begin() + cut[k + 1]);
+      const std::vector<size_t> ws = window_wants(by_doc, cut[k], cut[k + 1]);
+      if (ws.empty()) continue;  // (documents whose every op is refused before it looks at the document)
+      if (const int rc = write_pass(e, dl, cut[k], ops, wants, ws, S.device_ms)) return rc;
     }
     // a flagged op, or a failed one that is not its document's last (the clocks behind it assumed it
     // took its own), sends the document to the single calls
@@ -5151,16 +5042,9 @@ int ycrdt_docs_write(ycrdt_engine* e, const ycrdt_write* ops, size_t n, ycrdt_ou
     if (path == K_DEV) ++S.ops_device; else if (path == K_EMPTY) ++S.ops_empty; else ++S.ops_single;
     if (upd[i]->empty() && codes[i] == YCRDT_OK) ++S.ops_noop;
   }
-  uint64_t total = 0;
-  for (size_t i = 0; i < n; ++i) { offs[i] = total; total += upd[i]->size(); }
-  offs[n] = total;
-  uint8_t* out = (uint8_t*)malloc(total ? total : 1);
-  if (!out) return fail(YCRDT_E_CAPACITY, "host allocation failed");
-  for (size_t i = 0; i < n; ++i)
-    if (!upd[i]->empty()) memcpy(out + offs[i], upd[i]->data(), upd[i]->size());
-  blob->ptr = out;
-  blob->len = total;
-  S.out_bytes = total;
+  std::vector<BlobPart> parts(n);
+  for (size_t i = 0; i < n; ++i) parts[i] = part_of(*upd[i]);
+  if (const int rc = give_blob(parts, blob, offs, S.out_bytes)) return rc;
   if (st) *st = S;
   return YCRDT_OK;
 }

@@ -1,5 +1,6 @@
 // yc_engine_host.h — the engine host layer's helpers that make no HIP call: state-vector parsing, the
-// byte layout of a doc's marks block. The header builds with a plain C++ compiler (tests/csrc/engine_host_main.cpp runs it under the sanitizers).
+// byte layout of a doc's marks block, and what the calls over many documents share (the bytes of a device
+// pass, the pass windows, 64-byte aligned layouts, the answer blob). The header builds with a plain C++ compiler (tests/csrc/engine_host_main.cpp runs it under the sanitizers).
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -78,6 +79,58 @@ inline MarksLayout marks_layout(uint32_t nw, uint32_t cap, size_t section_bytes)
   m.meta = m.secs + section_bytes * cap;
   m.bytes = m.meta + 16;
   return m;
+}
+
+// ---- shared by the calls over many documents (ycrdt_docs_json / _cache / _read / _write / _diff)
+
+// Resident state bytes merged per device pass: `cap`, or what the call's environment variable `env`
+// asks for (tests shrink a pass to run the several-pass path on a few documents): unset or 0 is the
+// cap, and no value exceeds it.
+inline uint64_t pass_bytes(const char* env, uint64_t cap) {
+  const uint64_t x = env ? strtoull(env, nullptr, 10) : 0;
+  return x ? std::min(x, cap) : cap;
+}
+
+// The device passes over documents of the state lengths `lens`: documents in call order, as many as
+// one pass holds (each padded to 64 bytes, 64 spare), a window never empty. Window k is the documents
+// [cut[k], cut[k + 1]); no documents: no window.
+inline std::vector<size_t> pass_windows(const std::vector<uint64_t>& lens, uint64_t pass_bytes) {
+  std::vector<size_t> cut{0};
+  uint64_t bytes = 0;
+  for (size_t j = 0; j < lens.size(); ++j) {
+    if (j > cut.back() && bytes + lens[j] + 64 > pass_bytes) { cut.push_back(j); bytes = 0; }
+    bytes += (lens[j] + 63) & ~uint64_t(63);
+  }
+  if (!lens.empty()) cut.push_back(lens.size());
+  return cut;
+}
+
+// offsets of consecutive regions, each starting on a 64-byte line; `at` is the size so far
+struct Lay {
+  uint64_t at = 0;
+  uint64_t operator()(uint64_t bytes) {
+    const uint64_t o = at;
+    at = (at + bytes + 63) & ~uint64_t(63);
+    return o;
+  }
+};
+
+// The answer blob of a call: the parts back to back in one malloc'ed block, part i at offs[i], the
+// total at offs[parts.size()] and in `total`. A zero total gives a one-byte block; nullptr: the
+// allocation failed.
+struct BlobPart {
+  const void* p;
+  size_t len;
+};
+inline uint8_t* pack_blob(const std::vector<BlobPart>& parts, uint64_t* offs, uint64_t& total) {
+  total = 0;
+  for (size_t i = 0; i < parts.size(); ++i) { offs[i] = total; total += parts[i].len; }
+  offs[parts.size()] = total;
+  uint8_t* out = (uint8_t*)malloc(total ? total : 1);
+  if (!out) return nullptr;
+  for (size_t i = 0; i < parts.size(); ++i)
+    if (parts[i].len) memcpy(out + offs[i], parts[i].p, parts[i].len);
+  return out;
 }
 
 }  // namespace yc

@@ -4,6 +4,11 @@
 //   sv <hex|->                       parse_sv_sorted: "bad", or "ok client:clock ..."
 //   marks <nw> <cap>                 marks_layout over a heap block of exactly its size, every region written
 //                                    at its offset: the offsets of fbits sbits secs meta, the size
+//   passbytes <unset|empty|text> <cap>  pass_bytes over the environment's text (unset: a null pointer, empty: "")
+//   windows <pass_bytes> <len> ...   pass_windows: "[a,b) ..." one per window, or "none"
+//   lay <bytes> ...                  Lay: the offset of every region, then the size
+//   blob <hex|-> ...                 pack_blob over the parts, each in a heap block of its exact size: the
+//                                    total, every offset, the blob's bytes (a zero total: its one byte is written)
 #include <cstdio>
 #include <cstring>
 #include <memory>
@@ -51,6 +56,45 @@ int main() {
       memset(block.get() + at.secs, 3, 32ull * cap);
       memset(block.get() + at.meta, 4, 16);
       printf("fbits 0 sbits %zu secs %zu meta %zu bytes %zu nw %u cap %u\n", at.sbits, at.secs, at.meta, at.bytes, nw, cap);
+    } else if (cmd == "passbytes") {
+      uint64_t cap = 0;
+      in >> tok >> cap;
+      const std::string text = tok == "empty" ? "" : tok;
+      printf("%llu\n", (unsigned long long)yc::pass_bytes(tok == "unset" ? nullptr : text.c_str(), cap));
+    } else if (cmd == "windows") {
+      uint64_t pass = 0, len = 0;
+      in >> pass;
+      std::vector<uint64_t> lens;
+      while (in >> len) lens.push_back(len);
+      const std::vector<size_t> cut = yc::pass_windows(lens, pass);
+      if (cut.size() < 2) printf("none");
+      for (size_t k = 0; k + 1 < cut.size(); ++k) printf("%s[%zu,%zu)", k ? " " : "", cut[k], cut[k + 1]);
+      printf("\n");
+    } else if (cmd == "lay") {
+      yc::Lay lay;
+      uint64_t bytes = 0;
+      while (in >> bytes) printf("%llu ", (unsigned long long)lay(bytes));
+      printf("size %llu\n", (unsigned long long)lay.at);
+    } else if (cmd == "blob") {
+      std::vector<std::vector<uint8_t>> bytes;
+      std::vector<std::unique_ptr<uint8_t[]>> blocks;
+      std::vector<yc::BlobPart> parts;
+      while (in >> tok) {
+        bytes.push_back(unhex(tok));
+        blocks.push_back(exact(bytes.back()));
+        parts.push_back(yc::BlobPart{blocks.back().get(), bytes.back().size()});
+      }
+      std::unique_ptr<uint64_t[]> offs(new uint64_t[parts.size() + 1]);
+      uint64_t total = 99;
+      uint8_t* blob = yc::pack_blob(parts, offs.get(), total);
+      if (!blob) { printf("null\n"); continue; }
+      if (!total) blob[0] = 0;
+      printf("total %llu offs", (unsigned long long)total);
+      for (size_t i = 0; i <= parts.size(); ++i) printf(" %llu", (unsigned long long)offs[i]);
+      printf(" bytes %s", total ? "" : "-");
+      for (uint64_t i = 0; i < total; ++i) printf("%02x", blob[i]);
+      printf("\n");
+      free(blob);
     } else {
       printf("? %s\n", cmd.c_str());
     }
