@@ -135,6 +135,24 @@ class WriteStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class TransactStats(ctypes.Structure):
+    _fields_ = [
+        ("ops_device", ctypes.c_uint64),
+        ("ops_single", ctypes.c_uint64),
+        ("ops_empty", ctypes.c_uint64),
+        ("ops_noop", ctypes.c_uint64),
+        ("ops_chained", ctypes.c_uint64),
+        ("out_bytes", ctypes.c_uint64),
+        ("ranges_max", ctypes.c_uint32),
+        ("name_max", ctypes.c_uint32),
+        ("chain_max", ctypes.c_uint32),
+        ("device_ms", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class _Write(ctypes.Structure):  # ycrdt_write
     _fields_ = [
         ("doc", ctypes.c_void_p),
@@ -218,7 +236,7 @@ EXPORTS = (
     "ycrdt_comm_unique_id", "ycrdt_comm_create", "ycrdt_comm_destroy", "ycrdt_batch_merge_sharded",
     "ycrdt_comm_sv_allreduce_max", "ycrdt_comm_ds_allgather", "ycrdt_comm_create_exchange", "ycrdt_route",
     "ycrdt_comm_fleet_sv_allreduce_max", "ycrdt_docs_states_packed", "ycrdt_comm_allgather", "ycrdt_device_count",
-    "ycrdt_docs_diff", "ycrdt_docs_json", "ycrdt_docs_read", "ycrdt_docs_write", "ycrdt_docs_cache",
+    "ycrdt_docs_diff", "ycrdt_docs_json", "ycrdt_docs_read", "ycrdt_docs_write", "ycrdt_docs_transact", "ycrdt_docs_cache",
     "ycrdt_merge_updates_groups", "ycrdt_updates_state_vectors", "ycrdt_update_state_vector",
 )
 
@@ -303,6 +321,7 @@ def lib():
     L.ycrdt_docs_cache.argtypes = [vp, P(vp), sz, cs, P(_Out), P(ctypes.c_uint64), P(CacheStats)]
     L.ycrdt_docs_read.argtypes = [vp, P(_Read), sz, P(_Out), P(ctypes.c_uint64), P(ctypes.c_int32), P(ctypes.c_uint64), P(ReadStats)]
     L.ycrdt_docs_write.argtypes = [vp, P(_Write), sz, P(_Out), P(ctypes.c_uint64), P(ctypes.c_int32), P(WriteStats)]
+    L.ycrdt_docs_transact.argtypes = [vp, P(_Write), sz, P(_Out), P(ctypes.c_uint64), P(ctypes.c_int32), P(TransactStats)]
     L.ycrdt_merge_updates_groups.argtypes = [vp, P(_Buf), P(u32), sz, u32, P(_Out), P(ctypes.c_uint64), P(StoreStats)]
     L.ycrdt_updates_state_vectors.argtypes = [vp, P(_Buf), sz, P(_Out), P(ctypes.c_uint64), P(StoreStats)]
     L.ycrdt_update_state_vector.argtypes = [vp, _Buf, P(_Out)]
@@ -1014,16 +1033,8 @@ def docs_read(reads, engine=None) -> list:
     return docs_read_stats(reads, engine)[0]
 
 
-def docs_write_stats(ops, engine=None):
-    """(updates, codes, stats) of many local ops in one device pass (ycrdt_docs_write): the `set` /
-    `del` / `push` / `insert` / `cut` of crdt.js:423-611 batched over documents. ops: tuples
-    (op, doc, root, arg, parent_key_or_None); arg mirrors the single call of the op:
-    "map_set" (key, any_bytes) | "map_set_type" (key, type_ref) | "map_delete" key |
-    "array_insert" (index, [any_bytes, ...]) | "array_push" [any_bytes, ...] |
-    "array_delete" (index, length). updates[i] is the update Doc.<op> would have enqueued (b"" where
-    it writes nothing), codes[i] what the single call returns (0, or YCRDT_E_ARG where Doc.<op>
-    raises YcrdtError of kind "ARG"). Every non-empty update is enqueued as a local transaction. A
-    document may repeat: its ops run in order. stats: ycrdt_write_stats as a dict."""
+def _docs_write_call(call, st, ops, engine):
+    """ycrdt_docs_write / ycrdt_docs_transact (`call`, with its stats struct `st`) over docs_write_stats' op tuples."""
     import numpy as np
 
     def enc(x):
@@ -1061,9 +1072,8 @@ def docs_write_stats(ops, engine=None):
     offs = np.zeros(n + 1, dtype=np.uint64)
     codes = np.zeros(max(n, 1), dtype=np.int32)
     out = _Out()
-    st = WriteStats()
-    _check(lib().ycrdt_docs_write(eng._h, arr, n, ctypes.byref(out), offs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
-                                  codes.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), ctypes.byref(st)))
+    _check(call(eng._h, arr, n, ctypes.byref(out), offs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+                codes.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), ctypes.byref(st)))
     try:
         o = offs.tolist()
         blob = ctypes.string_at(out.ptr, out.len) if out.len else b""
@@ -1072,9 +1082,37 @@ def docs_write_stats(ops, engine=None):
         lib().ycrdt_free(ctypes.byref(out))
 
 
+def docs_write_stats(ops, engine=None):
+    """(updates, codes, stats) of many local ops in one device pass (ycrdt_docs_write): the `set` /
+    `del` / `push` / `insert` / `cut` of crdt.js:423-611 batched over documents. ops: tuples
+    (op, doc, root, arg, parent_key_or_None); arg mirrors the single call of the op:
+    "map_set" (key, any_bytes) | "map_set_type" (key, type_ref) | "map_delete" key |
+    "array_insert" (index, [any_bytes, ...]) | "array_push" [any_bytes, ...] |
+    "array_delete" (index, length). updates[i] is the update Doc.<op> would have enqueued (b"" where
+    it writes nothing), codes[i] what the single call returns (0, or YCRDT_E_ARG where Doc.<op>
+    raises YcrdtError of kind "ARG"). Every non-empty update is enqueued as a local transaction. A
+    document may repeat: its ops run in order. stats: ycrdt_write_stats as a dict."""
+    return _docs_write_call(lib().ycrdt_docs_write, WriteStats(), ops, engine)
+
+
 def docs_write(ops, engine=None):
     """(updates, codes) of docs_write_stats."""
     return docs_write_stats(ops, engine)[:2]
+
+
+def docs_transact_stats(ops, engine=None):
+    """docs_write_stats for ops that depend on one another (ycrdt_docs_transact): the queue that
+    crdt.js:329-355 (execBatch) runs in one doc.transact, for many documents at once. The same op
+    tuples; updates[i] is the update Doc.<op> would have enqueued had the call's earlier ops on that
+    document already run, codes[i] its result. Two ops of one map entry or one list, and a
+    "map_set_type" followed by ops under its key, stay on the device. stats: ycrdt_transact_stats as
+    a dict (ops_chained: the device ops planned through an earlier op of the call)."""
+    return _docs_write_call(lib().ycrdt_docs_transact, TransactStats(), ops, engine)
+
+
+def docs_transact(ops, engine=None):
+    """(updates, codes) of docs_transact_stats."""
+    return docs_transact_stats(ops, engine)[:2]
 
 
 def docs_diff(docs, svs, engine=None) -> list:

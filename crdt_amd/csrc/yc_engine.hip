@@ -4744,6 +4744,7 @@ struct WriteWant {           // one op of the device path
   int32_t why = 0;           // WHY_*
   std::vector<uint8_t> update;
   bool refused = false;
+  WriteLink link{WRITE_NONE, WRITE_NONE, WRITE_NONE, WHY_OK};  // ycrdt_docs_transact: indices into the call's wants
 };
 
 const char* str_or_empty(const char* s) { return s ? s : ""; }
@@ -4751,9 +4752,10 @@ const char* str_or_empty(const char* s) { return s ? s : ""; }
 // One device pass: the toJSON front half over the documents dl (the call's device documents from
 // `first` on), the visible scan of the reads, then the ops `ws` (indices into `wants`, their
 // documents all in dl) planned, sized and written. An op the device refuses is left `refused`: its
-// document goes through the single calls.
+// document goes through the single calls. `transact`: the ops are planned behind the earlier ops of
+// their call (k_tplan over the wants' links) instead of against the state before the call (k_wplan).
 int write_pass(ycrdt_engine* e, const std::vector<ycrdt_doc*>& dl, size_t first, const ycrdt_write* ops,
-               std::vector<WriteWant>& wants, const std::vector<size_t>& ws, double& device_ms) {
+               std::vector<WriteWant>& wants, const std::vector<size_t>& ws, bool transact, double& device_ms) {
   auto refuse_all = [&]() { for (size_t k : ws) wants[k].refused = true; return YCRDT_OK; };
   const uint32_t nr = (uint32_t)ws.size();
   // the distinct (document, root) of the ops
@@ -4798,6 +4800,21 @@ int write_pass(ycrdt_engine* e, const std::vector<ycrdt_doc*>& dl, size_t first,
   }
   std::vector<uint8_t> up(sizeof(WriteReq) * (size_t)nr);
   memcpy(up.data(), wr.data(), up.size());
+  if (transact) {  // the links behind the ops, as indices into this pass's ops (a document's ops share a pass)
+    auto local = [&](uint32_t k) {  // (a pass's wants are consecutive; one not in the pass: the kernel refuses the link)
+      if (k == WRITE_NONE) return WRITE_NONE;
+      const size_t r = (size_t)k - ws[0];
+      return k >= ws[0] && r < nr && ws[r] == k ? (uint32_t)r : WRITE_NONE - 1;
+    };
+    std::vector<WriteLink> links(nr);
+    for (uint32_t r = 0; r < nr; ++r) {
+      const WriteLink& l = wants[ws[r]].link;
+      links[r] = WriteLink{local(l.prev_entry), local(l.prev_list), local(l.creator), l.why};
+    }
+    static_assert(sizeof(WriteReq) % alignof(WriteLink) == 0, "the links follow the ops in one upload");
+    up.resize(up.size() + sizeof(WriteLink) * (size_t)nr);
+    memcpy(up.data() + sizeof(WriteReq) * (size_t)nr, links.data(), sizeof(WriteLink) * (size_t)nr);
+  }
   // the pass's own workspace: | offsets | reasons | flags | (read back together) and the rest
   Lay lay;
   const uint64_t rb_bytes = 8ull * (nr + 1) + 4ull * nr + 4ull * nr;
@@ -4834,7 +4851,8 @@ int write_pass(ycrdt_engine* e, const std::vector<ycrdt_doc*>& dl, size_t first,
   Wa.j = A;
   launch_read_visible(R, s);
   scan_u32_to_u64(F.tmp, F.tmpb, R.vis, R.scan_v, n + 1, s);
-  launch_write_plan(Wa, s);
+  if (transact) launch_transact_plan(Wa, (const WriteLink*)(F.xu + sizeof(WriteReq) * (size_t)nr), s);
+  else launch_write_plan(Wa, s);
   scan_u32_to_u64(F.tmp, F.tmpb, Wa.size, Wa.offs, (uint64_t)nr + 1, s);
   // the first read-back: offsets (the total is the last), reasons, flags, the view's counters
   std::vector<uint8_t> rb(rb_bytes);
@@ -4919,10 +4937,12 @@ bool writes_independent(const ycrdt_write* ops, const std::vector<size_t>& is, c
   return true;
 }
 
-}  // namespace
-
-int ycrdt_docs_write(ycrdt_engine* e, const ycrdt_write* ops, size_t n, ycrdt_out* blob, uint64_t* offs, int32_t* codes,
-                     ycrdt_write_stats* st) {
+// ycrdt_docs_write and ycrdt_docs_transact: one call, which differs in the documents that stay on
+// the device. `transact`: ops that depend on one another are planned through one another
+// (transact_links, k_tplan); else their document takes the single calls. `publish` hands the stats
+// out: once with the constants alone, once at the end.
+int docs_write_call(ycrdt_engine* e, const ycrdt_write* ops, size_t n, ycrdt_out* blob, uint64_t* offs, int32_t* codes, bool transact,
+                    const std::function<void(const ycrdt_transact_stats&)>& publish) {
   if (!e || !blob || !offs || (n && (!ops || !codes))) return fail(YCRDT_E_ARG, "null arg");
   for (size_t i = 0; i < n; ++i) {
     const ycrdt_write& q = ops[i];
@@ -4930,10 +4950,11 @@ int ycrdt_docs_write(ycrdt_engine* e, const ycrdt_write* ops, size_t n, ycrdt_ou
     if (!q.root) return fail(YCRDT_E_ARG, "null root at " + std::to_string(i));
     if (q.op < YCRDT_WRITE_MAP_SET || q.op > YCRDT_WRITE_ARRAY_DELETE) return fail(YCRDT_E_ARG, "op outside the six at " + std::to_string(i));
   }
-  ycrdt_write_stats S{};
+  ycrdt_transact_stats S{};
   S.ranges_max = WRITE_RANGES_MAX;
   S.name_max = JSON_NAME_MAX;
-  if (st) *st = S;
+  S.chain_max = WRITE_CHAIN_MAX;
+  publish(S);
   int rc0;
   if (blob_start(n, "too many ops", blob, offs, rc0)) return rc0;
   HIPCHK(hipSetDevice(e->device));
@@ -4943,7 +4964,7 @@ int ycrdt_docs_write(ycrdt_engine* e, const ycrdt_write* ops, size_t n, ycrdt_ou
     if (const int rc = flush_queued(e, docs.data(), n)) return rc;
   }
   // the call's documents and the path each takes: all ops of one document take the same one
-  const bool off = env_off("YCRDT_DOCS_WRITE");
+  const bool off = env_off(transact ? "YCRDT_DOCS_TRANSACT" : "YCRDT_DOCS_WRITE");
   std::vector<uint8_t> bad(n, 0);
   for (size_t i = 0; i < n; ++i) bad[i] = write_args_bad(ops[i]) ? 1 : 0;
   std::unordered_map<const ycrdt_doc*, uint32_t> cix;
@@ -4971,7 +4992,16 @@ int ycrdt_docs_write(ycrdt_engine* e, const ycrdt_write* ops, size_t n, ycrdt_ou
       if (q.parent_key && strlen(q.parent_key) > JSON_NAME_MAX) fits = false;
       if (q.op <= YCRDT_WRITE_MAP_DELETE && strlen(q.key) > JSON_NAME_MAX) fits = false;
     }
-    if (!fits || (cops[c].size() > 1 && !writes_independent(ops, cops[c], bad))) continue;
+    if (!fits) continue;
+    std::vector<WriteLink> links;  // transact: per op of the document that is not `bad`, indices among those
+    if (cops[c].size() > 1 && transact) {
+      std::vector<TransactOp> tx;
+      for (size_t i : cops[c])
+        if (!bad[i]) tx.push_back(TransactOp{ops[i].op, ops[i].root, ops[i].parent_key, ops[i].key, ops[i].type_ref});
+      if (transact_links(tx, links) > WRITE_CHAIN_MAX) continue;
+    } else if (cops[c].size() > 1 && !writes_independent(ops, cops[c], bad)) {
+      continue;
+    }
     kind[c] = K_DEV;
     // op k of the document takes the clock next + the lengths of its earlier item ops
     uint32_t clock = next_clock(d);
@@ -4984,6 +5014,12 @@ int ycrdt_docs_write(ycrdt_engine* e, const ycrdt_write* ops, size_t n, ycrdt_ou
       w.doc = (uint32_t)dlist.size();
       w.clock = clock;
       clock += q.op <= YCRDT_WRITE_MAP_SET_TYPE ? 1u : q.op == YCRDT_WRITE_ARRAY_INSERT || q.op == YCRDT_WRITE_ARRAY_PUSH ? q.count : 0u;
+      if (!links.empty()) {
+        const std::vector<size_t>& mine = by_doc.back();  // the document's wants so far: a link points at one of them
+        auto want = [&](uint32_t k) { return k == WRITE_NONE ? WRITE_NONE : (uint32_t)mine[k]; };
+        const WriteLink& l = links[mine.size()];
+        w.link = WriteLink{want(l.prev_entry), want(l.prev_list), want(l.creator), l.why};
+      }
       want_of[i] = wants.size();
       by_doc.back().push_back(wants.size());
       wants.push_back(std::move(w));
@@ -4993,12 +5029,19 @@ int ycrdt_docs_write(ycrdt_engine* e, const ycrdt_write* ops, size_t n, ycrdt_ou
   // device passes: documents in call order, as many as one window holds
   if (!wants.empty()) {
     // (tests shrink a pass through YCRDT_DOCS_WRITE_PASS_BYTES, as YCRDT_DOCS_READ_PASS_BYTES does)
-    const std::vector<size_t> cut = doc_windows(dlist, pass_bytes(getenv("YCRDT_DOCS_WRITE_PASS_BYTES"), JSON_PASS_BYTES));
+    const std::vector<size_t> cut =
+        doc_windows(dlist, pass_bytes(getenv(transact ? "YCRDT_DOCS_TRANSACT_PASS_BYTES" : "YCRDT_DOCS_WRITE_PASS_BYTES"), JSON_PASS_BYTES));
     for (size_t k = 0; k + 1 < cut.size(); ++k) {
       const std::vector<ycrdt_doc*> dl(dlist.begin() + cut[k], dlist.begin() + cut[k + 1]);
       const std::vector<size_t> ws = window_wants(by_doc, cut[k], cut[k + 1]);
       if (ws.empty()) continue;  // (documents whose every op is refused before it looks at the document)
-      if (const int rc = write_pass(e, dl, cut[k], ops, wants, ws, S.device_ms)) return rc;
+      // (a pass none of whose ops has a link is §5.2f's: k_wplan plans it)
+      bool linked = false;
+      for (size_t w : ws) {
+        const WriteLink& l = wants[w].link;
+        linked = linked || l.prev_entry != WRITE_NONE || l.prev_list != WRITE_NONE || l.creator != WRITE_NONE || l.why != WHY_OK;
+      }
+      if (const int rc = write_pass(e, dl, cut[k], ops, wants, ws, transact && linked, S.device_ms)) return rc;
     }
     // a flagged op, or a failed one that is not its document's last (the clocks behind it assumed it
     // took its own), sends the document to the single calls
@@ -5032,6 +5075,8 @@ int ycrdt_docs_write(ycrdt_engine* e, const ycrdt_write* ops, size_t n, ycrdt_ou
         if (const int rc = apply_local(d, w.update)) return rc;
         upd[i] = &w.update;
       }
+      const WriteLink& l = w.link;
+      if (l.prev_entry != WRITE_NONE || l.prev_list != WRITE_NONE || l.creator != WRITE_NONE || l.why != WHY_OK) ++S.ops_chained;
     } else {
       const uint64_t seq = d->local_seq;
       const int rc = write_single(q);
@@ -5045,8 +5090,24 @@ int ycrdt_docs_write(ycrdt_engine* e, const ycrdt_write* ops, size_t n, ycrdt_ou
   std::vector<BlobPart> parts(n);
   for (size_t i = 0; i < n; ++i) parts[i] = part_of(*upd[i]);
   if (const int rc = give_blob(parts, blob, offs, S.out_bytes)) return rc;
-  if (st) *st = S;
+  publish(S);
   return YCRDT_OK;
+}
+
+}  // namespace
+
+int ycrdt_docs_write(ycrdt_engine* e, const ycrdt_write* ops, size_t n, ycrdt_out* blob, uint64_t* offs, int32_t* codes,
+                     ycrdt_write_stats* st) {
+  return docs_write_call(e, ops, n, blob, offs, codes, false, [st](const ycrdt_transact_stats& S) {
+    if (st) *st = ycrdt_write_stats{S.ops_device, S.ops_single, S.ops_empty, S.ops_noop, S.out_bytes, S.ranges_max, S.name_max, S.device_ms};
+  });
+}
+
+int ycrdt_docs_transact(ycrdt_engine* e, const ycrdt_write* ops, size_t n, ycrdt_out* blob, uint64_t* offs, int32_t* codes,
+                        ycrdt_transact_stats* st) {
+  return docs_write_call(e, ops, n, blob, offs, codes, true, [st](const ycrdt_transact_stats& S) {
+    if (st) *st = S;
+  });
 }
 
 // Per-key reads (YMap.get / has / size, YArray.length / get): the view's hash index, no JSON of

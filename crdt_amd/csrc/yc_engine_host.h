@@ -1,15 +1,19 @@
 // yc_engine_host.h — the engine host layer's helpers that make no HIP call: state-vector parsing, the
 // byte layout of a doc's marks block, and what the calls over many documents share (the bytes of a device
-// pass, the pass windows, 64-byte aligned layouts, the answer blob). The header builds with a plain C++ compiler (tests/csrc/engine_host_main.cpp runs it under the sanitizers).
+// pass, the pass windows, 64-byte aligned layouts, the answer blob, the dependencies among a transaction's ops). The header builds with a plain C++ compiler (tests/csrc/engine_host_main.cpp runs it under the sanitizers).
 #pragma once
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
+#include <string>
 #include <unordered_map>
 #include <utility>
 #include <vector>
+
+#include "yc_write_ops.h"  // WriteLink, WR_*, WHY_*
 
 #pragma GCC visibility push(hidden)
 namespace yc {
@@ -131,6 +135,74 @@ inline uint8_t* pack_blob(const std::vector<BlobPart>& parts, uint64_t* offs, ui
   for (size_t i = 0; i < parts.size(); ++i)
     if (parts[i].len) memcpy(out + offs[i], parts[i].p, parts[i].len);
   return out;
+}
+
+// ---- ycrdt_docs_transact: how the ops of ONE document in one call depend on one another
+struct TransactOp {          // what the analysis reads of an op (ycrdt_write's fields)
+  int op;                    // WR_*
+  const char* root;
+  const char* parent_key;    // nullptr: the root type
+  const char* key;           // the map ops
+  uint32_t type_ref;         // MAP_SET_TYPE
+};
+
+// For the ops of one document in call order: links[i] names the previous op on op i's map entry,
+// the previous op on its list, and the MAP_SET_TYPE of this call that made its container (indices
+// into ops; WRITE_NONE: none). A container is (root, parent_key, epoch): every op that writes the
+// root-map entry (root, key = P) starts a new epoch of (root, P). Behind a MAP_SET_TYPE of the kind
+// an op needs the container is new and empty; behind any other write there is none, and the op
+// fails as the single call does (links[i].why). Such an op stands in no chain. Returns the longest chain.
+inline uint32_t transact_links(const std::vector<TransactOp>& ops, std::vector<WriteLink>& links) {
+  auto id = [](std::initializer_list<const char*> parts) {  // lengths in front of the names (a null part apart from "")
+    std::string k;
+    for (const char* p : parts) {
+      const uint64_t len = p ? strlen(p) + 1 : 0;
+      k.append((const char*)&len, 8);
+      if (p) k += p;
+    }
+    return k;
+  };
+  struct Epoch { uint32_t n = 0, writer = WRITE_NONE; };  // writer: the latest op that wrote the root-map entry
+  std::unordered_map<std::string, Epoch> epochs;
+  std::unordered_map<std::string, uint32_t> last_entry, last_list;
+  std::vector<uint32_t> depth(ops.size(), 1);
+  uint32_t longest = ops.empty() ? 0 : 1;
+  links.assign(ops.size(), WriteLink{WRITE_NONE, WRITE_NONE, WRITE_NONE, WHY_OK});
+  for (uint32_t i = 0; i < ops.size(); ++i) {
+    const TransactOp& q = ops[i];
+    const bool map_op = q.op <= (int)WR_MAP_DELETE;
+    WriteLink& L = links[i];
+    uint32_t epoch = 0;
+    if (q.parent_key) {
+      const auto at = epochs.find(id({q.root, q.parent_key}));
+      if (at != epochs.end()) {
+        epoch = at->second.n;
+        const TransactOp& w = ops[at->second.writer];
+        if (w.op != (int)WR_MAP_SET_TYPE) L.why = WHY_NO_TYPE;
+        else if (w.type_ref != (map_op ? 1u : 0u)) L.why = WHY_MISMATCH;
+        else L.creator = at->second.writer;
+      }
+    }
+    if (L.why == WHY_OK) {
+      std::string container = id({q.root, q.parent_key});
+      container.append((const char*)&epoch, 4);
+      auto& last = map_op ? last_entry : last_list;
+      const std::string k = map_op ? container + id({q.key}) : container;
+      const auto at = last.find(k);
+      if (at != last.end()) {
+        (map_op ? L.prev_entry : L.prev_list) = at->second;
+        depth[i] = depth[at->second] + 1;
+        longest = std::max(longest, depth[i]);
+      }
+      last[k] = i;
+    }
+    if (map_op && !q.parent_key) {
+      Epoch& e = epochs[id({q.root, q.key})];
+      ++e.n;
+      e.writer = i;
+    }
+  }
+  return longest;
 }
 
 }  // namespace yc

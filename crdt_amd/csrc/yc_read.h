@@ -15,6 +15,13 @@ namespace yc {
 constexpr uint32_t READ_NAME_MAX = 64;       // = JSON_NAME_MAX: the name bytes the radix passes order by
 constexpr uint32_t READ_NONE = 0xFFFFFFFFu;
 
+// read flags: any one sends the read to the single call
+constexpr uint32_t RF_NAME = 1u;     // a root of another name shares the root's hash slot
+constexpr uint32_t RF_LONG = 2u;     // an entry name past READ_NAME_MAX stands where the request's would
+constexpr uint32_t RF_OPEN = 4u;     // the value is refused by the writer's bounds, or a view record is out of range
+constexpr uint32_t RF_SIZE = 8u;     // its text would pass 4 GiB
+constexpr uint32_t RF_SEED = 16u;    // another read's value is the same nested type
+
 // (group, name, length) x against y in the order the radix passes produce: group, then the first
 // READ_NAME_MAX name bytes big-endian and zero padded, then the whole name's length. <0, 0, >0.
 // `ly_order`: the length y sorts by, where it is not the ly bytes that ny holds (a search bound).
@@ -79,13 +86,6 @@ namespace yc {
 static_assert(READ_NAME_MAX == JSON_NAME_MAX, "the search compares what the radix passes ordered");
 
 enum : uint32_t { RD_MAP_GET = 0, RD_MAP_SIZE = 1, RD_ARRAY_GET = 2, RD_ARRAY_LENGTH = 3 };  // = YCRDT_READ_*
-
-// read flags: any one sends the read to the single call
-constexpr uint32_t RF_NAME = 1u;     // a root of another name shares the root's hash slot
-constexpr uint32_t RF_LONG = 2u;     // an entry name past READ_NAME_MAX stands where the request's would
-constexpr uint32_t RF_OPEN = 4u;     // the value is refused by the writer's bounds, or a view record is out of range
-constexpr uint32_t RF_SIZE = 8u;     // its text would pass 4 GiB
-constexpr uint32_t RF_SEED = 16u;    // another read's value is the same nested type
 
 struct ReadReq {             // one distinct read
   uint64_t index;            // RD_ARRAY_GET

@@ -373,7 +373,7 @@ function readMany(requests) {
 // throws (the engine keeps the last failed op's own text; an earlier one reads 'invalid argument').
 // Every distinct doc is marked changed once, so its observers fire as after one transaction.
 const WRITE_OPS = { mapSet: 0, mapSetType: 1, mapDelete: 2, arrayInsert: 3, arrayPush: 4, arrayDelete: 5 };
-function writeMany(ops) {
+function writeMany(ops, transact = false) {
   if (!Array.isArray(ops)) throw new TypeError('writeMany(ops[])');
   const num = (v, d = 0) => (v === undefined ? d : v);
   const opt = (v) => (v === undefined ? null : v);
@@ -394,11 +394,20 @@ function writeMany(ops) {
     return [q.doc._h, code, q.root, opt(q.parentKey), code <= 2 ? opt(q.key) : null, values, count, typeRef, num(q.index), num(q.length, code === 5 ? 1 : 0)];
   });
   for (const q of ops) settle(q.doc);
-  const [updates, codes, message] = binding.docsWrite(rows);
+  const [updates, codes, message] = transact ? binding.docsTransact(rows) : binding.docsWrite(rows);
   for (const d of new Set(ops.map((q) => q.doc))) if (!d._txn) markChanged(d, true);
   let lastFailed = -1;
   codes.forEach((c, i) => { if (c !== 0) lastFailed = i; });
   return updates.map((update, i) => ({ update, error: codes[i] === 0 ? null : i === lastFailed ? message : 'invalid argument' }));
+}
+
+// batch entry (not in Yjs): writeMany for queues whose ops depend on one another — what crdt.js:329-355
+// (execBatch) runs in one doc.transact per document, for many documents in one device pass: two ops
+// of one key or one list, `set(key, new Y.Array())` and the pushes into it (crdt.js:422-431). The
+// same op objects, the same result, every distinct doc marked changed once.
+function transactMany(ops) {
+  if (!Array.isArray(ops)) throw new TypeError('transactMany(ops[])');
+  return writeMany(ops, true);
 }
 
 function encodeStateVector(doc) {
@@ -421,7 +430,8 @@ module.exports = {
   cachesToJSON,
   cachesToJSONText,
   readMany,
-  writeMany,
+  writeMany: (ops) => writeMany(ops),
+  transactMany,
   mergeUpdates: (updates) => binding.mergeUpdates(updates),
   diffUpdate: (update, sv) => binding.diffUpdate(update, sv),
   // batch entry (not in Yjs): [Y.diffUpdate(u, sv) for each pair] in one device pass — the sync

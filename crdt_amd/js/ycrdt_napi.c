@@ -810,8 +810,10 @@ static napi_value js_docs_read(napi_env env, napi_callback_info info) {
  * over documents). An op is [doc, op (YCRDT_WRITE_*), root, parentKey | null, key | null,
  * values (encoded `any`s) | null, count, typeRef, index, length]. updates[i] is the update the op
  * enqueued (empty where it wrote nothing), codes[i] what its single call returns, message the last
- * failed op's text. */
-static napi_value js_docs_write(napi_env env, napi_callback_info info) {
+ * failed op's text.
+ * docsTransact(ops[]) is the same call through ycrdt_docs_transact: a document's ops may depend on
+ * one another (crdt.js:329-355 execBatch) and still run in the one pass. */
+static napi_value docs_write_call(napi_env env, napi_callback_info info, int transact) {
   size_t argc = 1;
   napi_value argv[1];
   CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
@@ -866,7 +868,7 @@ static napi_value js_docs_write(napi_env env, napi_callback_info info) {
   ycrdt_out blob = {NULL, 0};
   napi_value res = NULL;
   if (ok) {
-    int rc = ycrdt_docs_write(e, ops, n, &blob, offs, codes, NULL);
+    int rc = transact ? ycrdt_docs_transact(e, ops, n, &blob, offs, codes, NULL) : ycrdt_docs_write(e, ops, n, &blob, offs, codes, NULL);
     if (rc != YCRDT_OK) {
       throw_rc(env, rc);
     } else {
@@ -901,6 +903,8 @@ static napi_value js_docs_write(napi_env env, napi_callback_info info) {
   free(ops); free(offs); free(codes);
   return res;
 }
+static napi_value js_docs_write(napi_env env, napi_callback_info info) { return docs_write_call(env, info, 0); }
+static napi_value js_docs_transact(napi_env env, napi_callback_info info) { return docs_write_call(env, info, 1); }
 
 /* typeJson(doc, root, parentKey, kind) → toJSON of the root type (parentKey null) or of the YMap
  * (kind 0) / YArray (kind 1) stored under root[parentKey], reading that type's own list only */
@@ -1153,6 +1157,7 @@ static napi_value init(napi_env env, napi_value exports) {
       {"docsCache", NULL, js_docs_cache, NULL, NULL, NULL, napi_default, NULL},
       {"docsRead", NULL, js_docs_read, NULL, NULL, NULL, napi_default, NULL},
       {"docsWrite", NULL, js_docs_write, NULL, NULL, NULL, napi_default, NULL},
+      {"docsTransact", NULL, js_docs_transact, NULL, NULL, NULL, napi_default, NULL},
       {"typeJson", NULL, js_type_json, NULL, NULL, NULL, napi_default, NULL},
       {"mapEntries", NULL, js_map_entries, NULL, NULL, NULL, napi_default, NULL},
       {"mapSet", NULL, js_map_set, NULL, NULL, NULL, napi_default, NULL},

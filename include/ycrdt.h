@@ -280,6 +280,31 @@ typedef struct {
 } ycrdt_write_stats;
 int ycrdt_docs_write(ycrdt_engine *e, const ycrdt_write *ops, size_t n, ycrdt_out *blob, uint64_t *offs /* n + 1 */,
                      int32_t *codes /* n */, ycrdt_write_stats *st /* may be NULL */);
+/* ycrdt_docs_write for a queue of ops that depend on one another, as crdt.js:329-355 (execBatch)
+ * runs one per document: op i's update is byte for byte the one the single call of its kind would
+ * have enqueued had the call's earlier ops on that document already run, codes[i] that call's
+ * result. The op struct, the updates' enqueueing in call order, the argument errors, ops_noop,
+ * ops_empty and n == 0 are those of ycrdt_docs_write; the difference is only which documents stay
+ * on the device. Two ops of one map entry, of one list, or a MAP_SET_TYPE and the ops under its key
+ * (crdt.js:422-431: `new Y.Array()` under a fresh key, then a push into it) no longer send their
+ * document to the single calls: the host finds, per op, the previous op on its entry, on its list
+ * and the op that made its container, and one lane per op replays the earlier ops of its chain over
+ * a small piece table. ops_chained counts the device ops planned through an
+ * earlier op of the call. Still single (ops_single), per document: what ycrdt_docs_write sends
+ * there for reasons other than dependence (pending structs or delete set, compat 135, a state of
+ * 2 GiB, a name over name_max, an op the device flags), more than chain_max ops of the call on one
+ * list or one map entry, and a failed op that is not the document's last (the clocks behind it were
+ * handed out as if it took its own). YCRDT_DOCS_TRANSACT=0 sends every op to the single calls. */
+typedef struct {
+  uint64_t ops_device, ops_single, ops_empty, ops_noop;  /* as ycrdt_write_stats */
+  uint64_t ops_chained;   /* device ops planned through an earlier op of the same call */
+  uint64_t out_bytes;
+  uint32_t ranges_max, name_max;
+  uint32_t chain_max;     /* ops of one call on one container chain the device takes (constant) */
+  double device_ms;
+} ycrdt_transact_stats;
+int ycrdt_docs_transact(ycrdt_engine *e, const ycrdt_write *ops, size_t n, ycrdt_out *blob, uint64_t *offs /* n + 1 */,
+                        int32_t *codes /* n */, ycrdt_transact_stats *st /* may be NULL */);
 /* Runs the deferred applies now (every read does this implicitly). */
 int ycrdt_doc_flush(ycrdt_doc *d);
 /* Whether Yjs would hold pending structs (store.pendingStructs) / a pending delete set
