@@ -132,17 +132,6 @@ __device__ __forceinline__ void phase_sync() {
   __threadfence();
 }
 
-// a host switch set to 0 (the small-batch kernels' A/B toggles)
-inline bool env_off(const char* name) {
-  const char* v = getenv(name);
-  return v && v[0] == '0';
-}
-// a host switch set to 1 (paths that are off by default)
-inline bool env_on(const char* name) {
-  const char* v = getenv(name);
-  return v && v[0] == '1';
-}
-
 __device__ __forceinline__ void raise_err(uint32_t* err, uint32_t code) {
   atomicCAS(err, 0u, code);
 }

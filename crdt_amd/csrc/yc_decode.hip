@@ -2334,8 +2334,8 @@ __global__ void k_prewalk_check(Work w) {
   const uint32_t u = w.ulist[bi], f = w.ufail[u];
   if (w.ulen[u] && f != UF_PRE && f != UF_WALKED) raise_err(&w.ctr->err, ERR_CAPACITY);
 }
-void launch_chunks(const Work& w, hipStream_t s) {
-  if (w.nbig && !w.force_xtab && !env_off("YCRDT_PREWALK")) hipLaunchKernelGGL(k_prewalk, dim3(w.nbig / 64 + 1), dim3(64), 0, s, w);
+void launch_chunks(const Work& w, const Switches& sw, hipStream_t s) {
+  if (w.nbig && !w.force_xtab && sw.prewalk) hipLaunchKernelGGL(k_prewalk, dim3(w.nbig / 64 + 1), dim3(64), 0, s, w);
   if (w.walk_only) {  // (a sync reply's delta behind a doc state: the chunk kernels would find nothing to do)
     hipLaunchKernelGGL(k_prewalk_check, dim3(w.nbig / 64 + 1), dim3(64), 0, s, w);
     return;
@@ -2348,9 +2348,7 @@ void launch_chunks(const Work& w, hipStream_t s) {
                          (const uint32_t*)(r & 1 ? w.sexit : w.cexit), r & 1 ? w.cexit : w.sexit, r);
   }
   if (w.nbig) {
-    // (read per merge: tests compare the fast walks with k_walk alone)
-    const bool nofast = getenv("YCRDT_NO_FASTWALK") && getenv("YCRDT_NO_FASTWALK")[0] == '1';
-    if (!nofast && !w.force_xtab) {
+    if (!sw.no_fastwalk && !w.force_xtab) {  // (YCRDT_NO_FASTWALK=1: tests compare the fast walks with k_walk alone)
       hipLaunchKernelGGL(k_chunk_counts, dim3(w.ngroups / 256 + 1), dim3(256), 0, s, w);
       scan_u32_to_u64(w.tmp, w.tmp_bytes, w.ccnt, w.cpre, (uint64_t)w.ngroups + 1, s);
       scan_u32(w.tmp, w.tmp_bytes, w.coff, w.opre, (uint64_t)w.ngroups + 1, s);
@@ -2545,19 +2543,17 @@ __global__ __launch_bounds__(WR_LANES) void k_wrank(Work w, uint32_t cap) {
   for (uint32_t k = t; k < nw; k += WR_LANES) fbits[(ustart >> 6) + k] = bits[k];
 }
 
-bool wave_decode(const Work& w) {
+bool wave_decode(const Work& w, const Switches& sw) {
   // one lane per update when there are enough updates to fill wavefronts, else the ranked path;
-  // YCRDT_DIRECT_WAVE=1 / 0 forces one (read per merge: tests switch it)
-  const char* wd = getenv("YCRDT_DIRECT_WAVE");
-  const bool lane_direct = wd && (wd[0] == '1' || wd[0] == '0') ? wd[0] == '0' : w.nsmall >= WD_LANE_MIN;
+  // YCRDT_DIRECT_WAVE=1 / 0 forces one (tests switch it)
+  const bool lane_direct = sw.direct_wave == DirectWave::AUTO ? w.nsmall >= WD_LANE_MIN : sw.direct_wave == DirectWave::LANE;
   return w.nsmall && !lane_direct;
 }
-void launch_direct(const Work& w, hipStream_t s) {
+void launch_direct(const Work& w, const Switches& sw, hipStream_t s) {
   // YCRDT_WDECODE=settle: the wavefront-per-update chains of k_wdecode instead of the ranking
-  const char* wm = getenv("YCRDT_WDECODE");
   // (a split decode's share may take this path where the whole batch did not: no rank tables)
-  if (wave_decode(w) && ((wm && !strcmp(wm, "settle")) || !w.wlen)) hipLaunchKernelGGL(k_wdecode, dim3(w.nsmall), dim3(64), 0, s, w);
-  else if (wave_decode(w)) {
+  if (wave_decode(w, sw) && (sw.wdecode == WdecodeMode::SETTLE || !w.wlen)) hipLaunchKernelGGL(k_wdecode, dim3(w.nsmall), dim3(64), 0, s, w);
+  else if (wave_decode(w, sw)) {
     const uint32_t cap = std::min(std::max(w.small_max, 1u), WD_MAX);
     static const bool lds_set = [] {  // (dynamic LDS past 64 KB: up to the WD_MAX table set)
       const bool r = hipFuncSetAttribute((const void*)k_wrank, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wr_lds(WD_MAX)) == hipSuccess;
@@ -3109,16 +3105,15 @@ __global__ __launch_bounds__(256) void k_dsp_ranges(Work w) {
     dsp_ranges_group(w, i, lane);
   }
 }
-void launch_ds_grid(const Work& w, hipStream_t s) {
-  if (!w.nbig || !w.dsp_cnt || w.nbig + 1 > DSP_PLAN_LANES * 16) return;
-  // YCRDT_DS_GRID=0: every delete set on the wavefront (read per merge: tests compare the two)
-  if (const char* g = getenv("YCRDT_DS_GRID")) if (g[0] == '0') return;
+void launch_ds_grid(const Work& w, const Switches& sw, hipStream_t s) {
+  // (YCRDT_DS_GRID=0: every delete set on the wavefront; tests compare the two)
+  if (!w.nbig || !w.dsp_cnt || w.nbig + 1 > DSP_PLAN_LANES * 16 || !sw.ds_grid) return;
   hipMemsetAsync(w.dsp_cnt, 0, sizeof(uint32_t) * ((size_t)w.ngroups + 1), s);
   hipLaunchKernelGGL(k_dsp_plan, dim3(1), dim3(DSP_PLAN_LANES), 0, s, w);
   hipLaunchKernelGGL(k_dsp_count, dim3(DSP_GRID), dim3(256), 0, s, w);
   scan_u32(w.tmp, w.tmp_bytes, w.dsp_cnt, w.dsp_pre, (uint64_t)w.ngroups + 1, s);
   hipLaunchKernelGGL(k_dsp_vals, dim3(DSP_GRID), dim3(256), 0, s, w);
-  const uint32_t jumps = w.dsp_j && !env_off("YCRDT_DS_JUMP") ? 1u : 0u;  // (YCRDT_DS_JUMP=0: the lane-serial walk, A/B)
+  const uint32_t jumps = w.dsp_j && sw.ds_jump ? 1u : 0u;  // (YCRDT_DS_JUMP=0: the lane-serial walk, A/B)
   hipLaunchKernelGGL(k_dsp_headers, dim3(w.nbig / 64 + 1), dim3(64), 0, s, w, jumps);
   if (jumps) {
     hipLaunchKernelGGL(k_dsh_jump, dim3(w.dsh_grid, w.nbig), dim3(256), 0, s, w);
@@ -3211,17 +3206,17 @@ __global__ __launch_bounds__(COUNT_LANES) void k_count_ds_small(Work w, uint32_t
   block_scan_u32<COUNT_LANES>(w.scratch, w.ds_region, w.nupd + 1, part);
   if (t == 0) w.ctr->ds_region = w.ds_region[w.nupd];
 }
-bool count_ds_small(const Work& w, hipStream_t s) {
+bool count_ds_small(const Work& w, const Switches& sw, hipStream_t s) {
   const uint32_t nwords = (w.nbytes + 63) / 64;
-  if (env_off("YCRDT_DECODE_SMALL") || !w.nupd || nwords + 1 > COUNT_SMALL || w.nupd + 1 > COUNT_SMALL) return false;
+  if (!sw.decode_small || !w.nupd || nwords + 1 > COUNT_SMALL || w.nupd + 1 > COUNT_SMALL) return false;
   hipLaunchKernelGGL(k_count_ds_small, dim3(1), dim3(COUNT_LANES), 0, s, w, nwords);
   return true;
 }
 // the integrate path reads the ranges in their per-update regions (k_ds_apply); mergeUpdates /
 // diffUpdate (lazy) sort them, so there they are compacted into the dense table
-void launch_ds_decode(const Work& w, hipStream_t s) {
+void launch_ds_decode(const Work& w, const Switches& sw, hipStream_t s) {
   if (w.nupd == 0) return;
-  launch_ds_grid(w, s);
+  launch_ds_grid(w, sw, s);
   hipLaunchKernelGGL(k_ds_decode, dim3((w.nupd + 3) / 4), dim3(256), 0, s, w);
   if (!w.lazy) return;
   scan_u32(w.tmp, w.tmp_bytes, w.ds_count, w.ds_dense_off, w.nupd + 1, s);
@@ -3417,8 +3412,8 @@ __global__ __launch_bounds__(CT_LANES) void k_sections_small(Work w, uint32_t n,
     }
   }
 }
-bool sections_small(const Work& w, uint32_t nsections, uint64_t* key, uint32_t* val, uint32_t mask, hipStream_t s) {
-  if (env_off("YCRDT_DECODE_SMALL") || w.udoc || !nsections || (nsections != NONE && nsections > CT_SMALL) || mask + 1 > 16 * CT_SMALL) return false;
+bool sections_small(const Work& w, const Switches& sw, uint32_t nsections, uint64_t* key, uint32_t* val, uint32_t mask, hipStream_t s) {
+  if (!sw.decode_small || w.udoc || !nsections || (nsections != NONE && nsections > CT_SMALL) || mask + 1 > 16 * CT_SMALL) return false;
   hipLaunchKernelGGL(k_sections_small, dim3(1), dim3(CT_LANES), 0, s, w, nsections, key, val, mask);
   return true;
 }
@@ -3815,9 +3810,9 @@ static bool launch_struct_clock_lb(const Work& w, uint32_t nstructs, uint32_t st
   return true;
 }
 
-void launch_struct_decode(const Work& w, uint32_t nstructs, hipStream_t s) {
+void launch_struct_decode(const Work& w, const Switches& sw, uint32_t nstructs, hipStream_t s) {
   if (!nstructs) return;
-  const uint32_t group = env_off("YCRDT_SD_GROUP") ? 0u : 1u;  // (read per merge: A/B in one process)
+  const uint32_t group = sw.sd_group ? 1u : 0u;  // (YCRDT_SD_GROUP=0: A/B)
   hipLaunchKernelGGL(k_struct_decode, dim3((nstructs + SD_LANES - 1) / SD_LANES), dim3(SD_LANES), 0, s, w, nstructs, group);
   hipLaunchKernelGGL(k_struct_decode_deferred, dim3(std::min<uint32_t>(nstructs / 256 + 1, SD_DEFER_GRID)), dim3(256), 0, s, w);
 }
@@ -3899,9 +3894,8 @@ __global__ __launch_bounds__(DT_LANES) void k_decode_tail_small(Work w, uint32_t
 void launch_decode_tail_small(const Work& w, uint32_t nstructs, uint32_t nsections, hipStream_t s) {
   hipLaunchKernelGGL(k_decode_tail_small, dim3(1), dim3(DT_LANES), 0, s, w, nstructs, nsections);
 }
-bool decode_tail_small(const Work& w, uint32_t nstructs, uint32_t nsections, hipStream_t s) {
-  const bool off = env_off("YCRDT_DECODE_SMALL");  // (read per merge: A/B in one process)
-  if (off || !nstructs || nstructs > DT_SMALL || nsections + 1 > DT_LANES * 16) return false;
+bool decode_tail_small(const Work& w, const Switches& sw, uint32_t nstructs, uint32_t nsections, hipStream_t s) {
+  if (!sw.decode_small || !nstructs || nstructs > DT_SMALL || nsections + 1 > DT_LANES * 16) return false;
   hipLaunchKernelGGL(k_decode_tail_small, dim3(1), dim3(DT_LANES), 0, s, w, nstructs, nsections);
   return true;
 }

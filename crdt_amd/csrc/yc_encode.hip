@@ -653,9 +653,8 @@ __global__ __launch_bounds__(ENC_SMALL_LANES) void k_encode_small(Work w, uint32
   for (uint32_t c = t; c < max(nclients, 1u); c += ENC_SMALL_LANES) write_clients_at(w, c, nclients);
   for (uint32_t r = t; r < nruns; r += ENC_SMALL_LANES) write_runs_at(w, r);
 }
-bool encode_small_fits(uint64_t nsegs_bound, uint32_t nclients) {
-  const bool off = env_off("YCRDT_ENCODE_SMALL");  // (read per merge: A/B in one process)
-  return !off && nsegs_bound + 1 <= ENC_SMALL && nclients + 1 <= ENC_SMALL;
+bool encode_small_fits(const Switches& sw, uint64_t nsegs_bound, uint32_t nclients) {
+  return sw.encode_small && nsegs_bound + 1 <= ENC_SMALL && nclients + 1 <= ENC_SMALL;
 }
 // (nsegs: NONE = read on the device)
 void launch_encode_small(const Work& w, uint32_t nsegs, uint32_t nclients, hipStream_t s) {

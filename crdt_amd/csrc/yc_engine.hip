@@ -5,7 +5,9 @@
 // calls over many documents (their shared helpers first; json_front and what the toJSON, cache, read
 // and write passes share behind it stand with the toJSON call), the batch and comm ABI, local ops and
 // reads. The helpers that make no HIP call are in yc_engine_host.h (tested on the CPU): state vectors,
-// the marks block, pass bytes and windows, aligned layouts, the answer blob.
+// the marks block, pass bytes and windows, aligned layouts, the answer blob. The YCRDT_* environment
+// switches are read through yc_switches.h alone: a snapshot per staged batch (ycrdt_batch::sw, layout)
+// and per call over many documents.
 //
 // One engine = one HIP device + one stream + a grow-only set of HBM buffers. A merge runs the
 // decode → dedupe → delete-set → segmentation → map-winner → encode kernels back to back on the
@@ -281,6 +283,7 @@ struct ycrdt_doc {
 
 struct ycrdt_batch {
   ycrdt_engine* e = nullptr;
+  Switches sw;                  // the environment when the batch was staged (layout): every later pass reads this
   DevBuf bytes, meta, pieces;
   std::vector<uint32_t> uoff, ulen, ugroup;  // uoff: within the update's window (yc_work.h WIN_SHIFT)
   std::vector<uint32_t> uwin;   // window of every staged update
@@ -379,7 +382,13 @@ struct Src {
 
 // Lays out the sources (64-byte aligned, so every update owns its bitmap words; device sources
 // first, then the host ones in one contiguous region) + decode group table.
-void layout(ycrdt_batch* b, const std::vector<Src>& src, std::vector<uint32_t>& order) {
+void layout(ycrdt_batch* b, const std::vector<Src>& src, std::vector<uint32_t>& order, bool restage) {
+  if (!restage) b->sw = read_switches();  // (a re-stage after a JSON rewrite keeps the batch's switches)
+  const Switches& sw = b->sw;
+  if (b->pre_src >= 0) {  // what doc_pre offered, by YCRDT_PREDECODE
+    if (sw.predecode == Predecode::OFF) b->pre_src = -1;
+    b->pre_check = sw.predecode == Predecode::CHECK;
+  }
   b->uoff.clear(); b->ulen.clear(); b->ugroup.clear(); b->groups.clear(); b->ulist.clear(); b->uwin.clear();
   b->fwc_off.clear();
   b->fwc_recs = 0;
@@ -392,8 +401,7 @@ void layout(ycrdt_batch* b, const std::vector<Src>& src, std::vector<uint32_t>& 
   constexpr uint32_t FWC_MIN_SECTIONS = 16;
   constexpr uint64_t FWC_MAX_RECS = uint64_t(128) << 20;
   // (YCRDT_FWC=force, tests: every large update of two or more sections, however small)
-  const char* fwc_env = getenv("YCRDT_FWC");
-  const bool fwc_on = !env_off("YCRDT_FWC"), fwc_force = fwc_env && !strcmp(fwc_env, "force");
+  const bool fwc_on = sw.fwc != FwcMode::OFF, fwc_force = sw.fwc == FwcMode::FORCE;
   // Sections must also be short on average (<= FWC_MAX_SECTION bytes): the step table and the records
   // cost every byte, the walk they replace costs every section — a C3 state's 256 sections of 300 KB
   // each ran 13.7 -> 25.8 ms in record mode (a C2 document's 1 001 sections of 8 KB: 31 -> 4.5 ms)
@@ -407,9 +415,7 @@ void layout(ycrdt_batch* b, const std::vector<Src>& src, std::vector<uint32_t>& 
     if (fwc_force) return okq && nsec >= 2u;
     return okq && nsec >= FWC_MIN_SECTIONS && x.len <= (size_t)nsec * FWC_MAX_SECTION;
   };
-  const char* mode = getenv("YCRDT_DECODE");
-  const int force = mode && (!strcmp(mode, "chunks") || !strcmp(mode, "tables") || !strcmp(mode, "xtab")) ? 1
-                    : mode && !strcmp(mode, "direct") ? 2 : 0;
+  const int force = sw.decode == DecodeMode::AUTO ? 0 : sw.decode == DecodeMode::DIRECT ? 2 : 1;
   // (decoded by k_predecoded; a large one stays in the big list, its chunks serving the grid
   // delete-set decode only; a small one is in neither list)
   constexpr size_t PRE_GROUPS_MIN = size_t(64) << 10;
@@ -419,8 +425,7 @@ void layout(ycrdt_batch* b, const std::vector<Src>& src, std::vector<uint32_t>& 
   // small updates are parsed directly however few there are: one lane each (k_direct) when they
   // fill wavefronts, else one wavefront each (k_wdecode); YCRDT_DIRECT_WAVE=0 keeps the lane
   // kernel, and then few small updates take the chunk path as before
-  const char* wd = getenv("YCRDT_DIRECT_WAVE");
-  const bool lane_only = wd && wd[0] == '0';
+  const bool lane_only = sw.direct_wave == DirectWave::LANE;
   auto direct = [&](size_t len) {
     if (len > DIRECT_MAX_BYTES || force == 1) return false;
     return force == 2 || !lane_only || nsmall >= DIRECT_MIN_COUNT || len <= DIRECT_TINY_BYTES;
@@ -436,19 +441,13 @@ void layout(ycrdt_batch* b, const std::vector<Src>& src, std::vector<uint32_t>& 
     while (b->schunk > SCHUNK_SMALL && (size_t)(b->schunk / 2) * 64 >= big_max) b->schunk /= 2;
   else if (big_bytes <= MID_BATCH_BYTES)
     b->schunk = SCHUNK / 2;  // a single document's worth: more, shorter chunk chains (the walk is mostly the fast one)
-  if (const char* cs = getenv("YCRDT_SCHUNK")) {  // experiments: a fixed chunk size (64-byte multiple)
-    const uint32_t v = (uint32_t)atoi(cs);
-    if (v >= 64 && v <= SCHUNK && v % 64 == 0) b->schunk = v;
-  }
+  static_assert(SCHUNK_LIMIT == SCHUNK && WIN_SHIFT == 32, "yc_switches.h bounds YCRDT_SCHUNK and defaults YCRDT_WIN_SHIFT by these");
+  if (sw.schunk) b->schunk = sw.schunk;  // experiments: a fixed chunk size (64-byte multiple)
   order.clear();
   for (size_t i = 0; i < src.size(); ++i) if (src[i].dev) order.push_back((uint32_t)i);
   for (size_t i = 0; i < src.size(); ++i) if (!src[i].dev) order.push_back((uint32_t)i);
   std::vector<uint32_t> small;
-  b->win_shift = WIN_SHIFT;
-  if (const char* ws = getenv("YCRDT_WIN_SHIFT")) {  // tests: small windows (every multi-window path on MBs)
-    const int v = atoi(ws);
-    if (v >= 16 && v <= 32) b->win_shift = (uint32_t)v;  // (64 KiB: a few hundred small updates span several)
-  }
+  b->win_shift = sw.win_shift;  // tests: small windows (every multi-window path on MBs; 64 KiB: a few hundred small updates span several)
   const uint64_t wuse = win_use(b->win_shift);
   uint64_t total = 0, win = 0;  // total: bytes used in window `win`
   bool walk_all = true;
@@ -511,12 +510,7 @@ struct HostPiece {
   const uint8_t* p;
 };
 constexpr uint32_t PIN_PER = 4;  // 128 MiB waves: the copy of a wave overlaps the transfer of the previous
-// 32 MiB; YCRDT_PIN_CHUNK (tests: e.g. 65536) makes the two-half wave path run on small batches
-uint64_t pin_chunk() {
-  const char* v = getenv("YCRDT_PIN_CHUNK");
-  const uint64_t c = v ? strtoull(v, nullptr, 10) : 0;
-  return c >= 4096 && c <= (uint64_t(1) << 30) ? c : uint64_t(32) << 20;
-}
+// PIN_CHUNK: 32 MiB; YCRDT_PIN_CHUNK (tests: e.g. 65536) makes the two-half wave path run on small batches
 // copies the pieces overlapping [lo, hi) of the span to dst (= span byte lo), zero elsewhere
 void fill_range(uint8_t* dst, uint64_t lo, uint64_t hi, const std::vector<HostPiece>& hp) {
   size_t i = std::upper_bound(hp.begin(), hp.end(), lo, [](uint64_t v, const HostPiece& x) { return v < x.off; }) - hp.begin();
@@ -546,11 +540,10 @@ int ensure_pinned(Pinned& pin, size_t need, hipStream_t s) {
   pin.cap = c;
   return YCRDT_OK;
 }
-int h2d_span(ycrdt_engine* e, uint8_t* dev, uint64_t span, const std::vector<HostPiece>& hp) {
+int h2d_span(ycrdt_engine* e, uint64_t PIN_CHUNK, uint8_t* dev, uint64_t span, const std::vector<HostPiece>& hp) {
   if (!span) return YCRDT_OK;
   Pinned& pin = e->pin_in;
   const hipStream_t s = e->copy;
-  const uint64_t PIN_CHUNK = pin_chunk();
   const uint64_t nch = (span + PIN_CHUNK - 1) / PIN_CHUNK;
   const bool waves = nch > PIN_PER;
   if (const int rc = ensure_pinned(pin, waves ? 2 * PIN_PER * PIN_CHUNK : (size_t)span, s)) return rc;
@@ -584,11 +577,12 @@ int h2d_span(ycrdt_engine* e, uint8_t* dev, uint64_t span, const std::vector<Hos
 }
 
 // Stages the sources into the batch buffer: the host region in one H2D copy, device sources by
-// one piece-copy launch. doc_of (one per source) makes it a multi-document batch.
-int stage_srcs(ycrdt_batch* b, const std::vector<Src>& src, const uint32_t* doc_of = nullptr, uint32_t ndocs = 1) {
+// one piece-copy launch. doc_of (one per source) makes it a multi-document batch. restage: the
+// batch staged again with rewritten updates (json_rewrite), under the switches it was staged with.
+int stage_srcs(ycrdt_batch* b, const std::vector<Src>& src, const uint32_t* doc_of = nullptr, uint32_t ndocs = 1, bool restage = false) {
   ycrdt_engine* e = b->e;
   std::vector<uint32_t> order;
-  layout(b, src, order);
+  layout(b, src, order, restage);
   for (const Src& x : src)
     if (((x.len + 63) & ~size_t(63)) > win_use(b->win_shift)) return fail(YCRDT_E_CAPACITY, "an update larger than 4 GiB");
   if (b->nwin > 255) return fail(YCRDT_E_CAPACITY, "batch larger than 255 windows of 4 GiB");
@@ -611,7 +605,7 @@ int stage_srcs(ycrdt_batch* b, const std::vector<Src>& src, const uint32_t* doc_
     std::vector<HostPiece> hp;
     hp.reserve(nu - ndev);
     for (size_t u = ndev; u < nu; ++u) hp.push_back(HostPiece{uabs(b, u) - host0, b->ulen[u], src[order[u]].p});
-    if (const int rc = h2d_span(e, (uint8_t*)b->bytes.p + host0, b->nbytes - host0, hp)) return rc;
+    if (const int rc = h2d_span(e, b->sw.pin_chunk, (uint8_t*)b->bytes.p + host0, b->nbytes - host0, hp)) return rc;
   }
   if (ndev == 1) {
     if (b->ulen[0]) HIPCHK(hipMemcpyAsync(b->bytes.p, src[order[0]].p, b->ulen[0], hipMemcpyDeviceToDevice, cs));
@@ -947,7 +941,7 @@ int json_rewrite(ycrdt_engine* e, ycrdt_batch* b, uint32_t n, const ShardSpec* s
   const uint32_t ndocs = b->ndocs, ntrusted = b->ntrusted;
   b->pre_src = -1;  // (a doc state's marks no longer name a source: it is decoded like the others)
   b->pre_check = false;
-  if (const int rc = stage_srcs(b, src, udoc.empty() ? nullptr : udoc.data(), ndocs)) return rc;
+  if (const int rc = stage_srcs(b, src, udoc.empty() ? nullptr : udoc.data(), ndocs, true)) return rc;
   b->ntrusted = ntrusted;  // (the same updates in the same order, now all host copies)
   b->jstore = std::move(store);
   restaged = true;
@@ -992,19 +986,16 @@ int run_decode(ycrdt_engine* e, ycrdt_batch* b, bool lazy, Decoded& D, bool gene
   w.small_max = 0;
   for (size_t i = b->nbig; i < b->ulist.size(); ++i) w.small_max = std::max(w.small_max, b->ulen[b->ulist[i]]);
   w.lazy = lazy ? 1u : 0u;
-  {
-    const char* mode = getenv("YCRDT_DECODE");
-    w.force_xtab = mode && !strcmp(mode, "xtab") ? 1u : 0u;
-    // the chunk walk skipped when the pre-walk takes every large update (YCRDT_WALK_ONLY=0: A/B);
-    // a pre-walk that stops short raises a capacity error and the generous rerun walks the chunks
-    w.walk_only = b->walk_only && !generous && !sh && !w.force_xtab && !env_off("YCRDT_PREWALK") && !env_off("YCRDT_WALK_ONLY") ? 1u : 0u;
-    w.fwm_max = getenv("YCRDT_FWM_MAX") ? (uint32_t)atoi(getenv("YCRDT_FWM_MAX")) : 0u;
-    const char* sh = getenv("YCRDT_SPEC_HINT");
-    // chunk-start hints: single-section updates only by default (a C2 snapshot or replica update
-    // syncs with them; multi-section C4 states locked into wrong phases with them, §5.4b);
-    // YCRDT_SPEC_HINT=1 / 0: always / never
-    w.spec_hint = sh && sh[0] == '1' ? 1u : sh && sh[0] == '0' ? 0u : 2u;
-  }
+  const Switches& sw = b->sw;
+  w.force_xtab = sw.decode == DecodeMode::XTAB ? 1u : 0u;
+  // the chunk walk skipped when the pre-walk takes every large update (YCRDT_WALK_ONLY=0: A/B);
+  // a pre-walk that stops short raises a capacity error and the generous rerun walks the chunks
+  w.walk_only = b->walk_only && !generous && !sh && !w.force_xtab && sw.prewalk && sw.walk_only ? 1u : 0u;
+  w.fwm_max = sw.fwm_max;
+  // chunk-start hints: single-section updates only by default (a C2 snapshot or replica update
+  // syncs with them; multi-section C4 states locked into wrong phases with them, §5.4b);
+  // YCRDT_SPEC_HINT=1 / 0: always / never
+  w.spec_hint = (uint32_t)sw.spec_hint;
   const uint64_t B = (uint64_t)b->nbytes + 64;
   const uint64_t nwords = B / 64 + 2;
   // The section table is sized from an estimate (a capacity overflow reruns the decode with the
@@ -1013,8 +1004,8 @@ int run_decode(ycrdt_engine* e, ycrdt_batch* b, bool lazy, Decoded& D, bool gene
   const uint64_t est_sec = std::min<uint64_t>(generous ? B / 3 + 64 : std::min<uint64_t>(B / 3 + 64, (uint64_t)nu * 16 + B / 256 + 4096),
                                               0x7FFFFFFFull);
   w.cap_sections = (uint32_t)est_sec;
-  if (const char* tc = getenv("YCRDT_TEST_SECTION_CAP"))  // tests: a tiny estimate forces the overflow re-run
-    if (!generous && atoi(tc) > 0) w.cap_sections = std::min<uint32_t>(w.cap_sections, (uint32_t)atoi(tc));
+  // YCRDT_TEST_SECTION_CAP, tests: a tiny estimate forces the overflow re-run
+  if (sw.test_section_cap && !generous) w.cap_sections = std::min<uint32_t>(w.cap_sections, sw.test_section_cap);
   w.cap_structs = 0;
   w.cap_ds = 0;
   // ---- decode buffers
@@ -1051,7 +1042,7 @@ int run_decode(ycrdt_engine* e, ycrdt_batch* b, bool lazy, Decoded& D, bool gene
   w.scratch = take<uint32_t>(V, B_SCRATCH, std::max<uint64_t>({nwords + 2, (uint64_t)w.cap_sections + 66, (uint64_t)nu + 2}), ok);
   w.usec_start = take<uint32_t>(V, B_USEC, nu + 1, ok);
   w.usec_n = take<uint32_t>(V, B_USECN, nu + 1, ok);
-  w.wlen = wave_decode(w) ? take<uint16_t>(V, B_WLEN, (uint64_t)w.nsmall * 16384, ok) : nullptr;
+  w.wlen = wave_decode(w, sw) ? take<uint16_t>(V, B_WLEN, (uint64_t)w.nsmall * 16384, ok) : nullptr;
   w.fwsec = w.nbig ? take<uint32_t>(V, B_FWSEC, 2ull * w.cap_sections + 2, ok) : nullptr;
   w.fwc = nullptr;
   w.fwc_off = nullptr;
@@ -1062,10 +1053,9 @@ int run_decode(ycrdt_engine* e, ycrdt_batch* b, bool lazy, Decoded& D, bool gene
     uint32_t* fo = take<uint32_t>(V, B_FWCOFF, nu + 1, ok);
     if (ok) HIPCHK(hipMemcpyAsync(fo, b->fwc_off.data(), sizeof(uint32_t) * nu, hipMemcpyHostToDevice, e->stream));
     w.fwc_off = fo;
-    if (!env_off("YCRDT_RTAB")) w.rtab = take<uint32_t>(V, B_RTAB, b->fwc_recs + 1, ok);  // (YCRDT_RTAB=0: parse every step, A/B)
-    if (w.rtab && !env_off("YCRDT_RANK_LAST")) w.rk = take<uint4>(V, B_RK, nu + 1, ok);
-    const char* fw = getenv("YCRDT_FWC_WALK");  // (experiments)
-    w.fwc_walk = fw && atoi(fw) > 0 ? (uint32_t)atoi(fw) : 256u;
+    if (sw.rtab) w.rtab = take<uint32_t>(V, B_RTAB, b->fwc_recs + 1, ok);  // (YCRDT_RTAB=0: parse every step, A/B)
+    if (w.rtab && sw.rank_last) w.rk = take<uint4>(V, B_RK, nu + 1, ok);
+    w.fwc_walk = sw.fwc_walk;  // (YCRDT_FWC_WALK: experiments)
   }
   if (!ok) return fail(YCRDT_E_DEVICE, oom("decode workspace"));
   // rocPRIM scratch sized for the largest scan of this batch (units may grow it later)
@@ -1083,15 +1073,14 @@ int run_decode(ycrdt_engine* e, ycrdt_batch* b, bool lazy, Decoded& D, bool gene
                   {w.usec_n, (uint64_t)nu + 1, 0u},  // an update no walker reached has no sections
                   {(uint32_t*)w.final_bits, (uint64_t)nwords * 2, 0u},
                   {(uint32_t*)w.sec_bits, (uint64_t)nwords * 2, 0u}}, s);
-  w.dbg_bounds = env_on("YCRDT_DEBUG_BOUNDS") ? 1u : 0u;
-  w.scan_fused = env_off("YCRDT_SCAN_FUSED") ? 0u : 1u;  // (read per merge: A/B in one process)
+  w.dbg_bounds = sw.debug_bounds ? 1u : 0u;
+  w.scan_fused = sw.scan_fused ? 1u : 0u;  // (YCRDT_SCAN_FUSED=0: A/B)
   // the encode record (yc_encrec.h) holds a position within ONE window; YCRDT_ENC_RECORD=0: A/B, tests
-  w.enc_record = b->nwin <= 1 && !env_off("YCRDT_ENC_RECORD") ? 1u : 0u;
+  w.enc_record = b->nwin <= 1 && sw.enc_record ? 1u : 0u;
   w.upre = b->pre_src >= 0 && !b->pre_check ? b->pre_u : NONE;
   if (w.upre != NONE) launch_predecoded(w, b->pre_u, b->pre, false, s);  // (a doc state: its own encode's decode)
-  const bool dbg_yata = getenv("YCRDT_DEBUG_YATA") && getenv("YCRDT_DEBUG_YATA")[0] == '1';
-  const bool dbg_dec = getenv("YCRDT_DEBUG_DECODE") && getenv("YCRDT_DEBUG_DECODE")[0] == '1';
-  w.dbg = dbg_yata || dbg_dec ? take<unsigned long long>(V, B_DBG, 24, ok) : nullptr;
+  const bool dbg_dec = sw.debug_decode;
+  w.dbg = sw.debug_yata || dbg_dec ? take<unsigned long long>(V, B_DBG, 24, ok) : nullptr;
   if (w.dbg) HIPCHK(hipMemsetAsync(w.dbg, 0, 192, s));
   // ---- K1 decode
   // large updates (chunk path, mostly latency-bound) on the side stream, beside k_direct
@@ -1110,23 +1099,22 @@ int run_decode(ycrdt_engine* e, ycrdt_batch* b, bool lazy, Decoded& D, bool gene
   if (chunks) {
     HIPCHK(hipEventRecord(e->side_fork, s));
     HIPCHK(hipStreamWaitEvent(e->side, e->side_fork, 0));
-    launch_chunks(wd, e->side);
+    launch_chunks(wd, sw, e->side);
     HIPCHK(hipEventRecord(e->side_done, e->side));
   }
-  launch_direct(wd, s);
+  launch_direct(wd, sw, s);
   mark(e, "decode.chunk_wait");  // decode.direct: k_direct alone (the chunk path runs beside it)
   if (chunks) HIPCHK(hipStreamWaitEvent(s, e->side_done, 0));
   if (split) {
     mark(e, "decode.exchange");
     // test hook (tests/test_gpu_exchange.py): this rank fails on the host before the exchange
-    const char* fh = getenv("YCRDT_TEST_FAIL_BEFORE_EXCHANGE");
-    if (fh && fh[0] == '1') return fail(YCRDT_E_DEVICE, "test hook: failure before the decode exchange");
+    if (sw.test_fail_before_exchange) return fail(YCRDT_E_DEVICE, "test hook: failure before the decode exchange");
     const int rc0 = split_decode_exchange(e, b, sh);
     if (rc0 == YCRDT_E_CAPACITY && !generous) return run_decode(e, b, lazy, D, true, sh);  // every rank alike
     if (rc0) return rc0;
   }
   mark(e, "decode.bitmap");
-  if (!count_ds_small(w, s)) {  // (small batches: one workgroup)
+  if (!count_ds_small(w, sw, s)) {  // (small batches: one workgroup)
     launch_struct_count(w, s);
     launch_ds_bound(w, s);
   }
@@ -1138,7 +1126,7 @@ int run_decode(ycrdt_engine* e, ycrdt_batch* b, bool lazy, Decoded& D, bool gene
   // passes read the counts on the device, and one past their sizes raises a capacity error that
   // reruns the decode the counted way (generous)
   const bool quick = !lazy && !split && !generous && !w.dbg && !w.udoc && w.nupd && b->nwin <= 1 && w.nbytes <= (64u << 10) && w.cap_sections <= 16000 &&
-                     !env_off("YCRDT_DECODE_SMALL") && !env_off("YCRDT_DECODE_QUICK");
+                     sw.decode_small && sw.decode_quick;
   if (b->pre_src >= 0 && b->pre_check) launch_predecoded(w, b->pre_u, b->pre, true, s);  // (reported at the next check)
   int rc = quick ? YCRDT_OK : check(e, c, "decode");
   if (quick) {
@@ -1205,7 +1193,7 @@ int run_decode(ycrdt_engine* e, ycrdt_batch* b, bool lazy, Decoded& D, bool gene
   if (!ok) return fail(YCRDT_E_DEVICE, oom("struct table"));
   launch_struct_scatter(w, s);
   // small single-document batches: section ranks, client table and client hash in one launch
-  const bool sec_small = quick || (!w.udoc && nsections && nsections <= 2048 && ch_slots <= 8192 && !env_off("YCRDT_DECODE_SMALL"));
+  const bool sec_small = quick || (!w.udoc && nsections && nsections <= 2048 && ch_slots <= 8192 && sw.decode_small);
   if (!sec_small) launch_section_clients(w, nsections, s);
   mark(e, "decode.sections");
   {  // the delete sets decode on the side stream (own scratch / scan space) while the client
@@ -1245,11 +1233,11 @@ int run_decode(ycrdt_engine* e, ycrdt_batch* b, bool lazy, Decoded& D, bool gene
     }
     if (!okd) return fail(YCRDT_E_DEVICE, oom("delete-set scratch"));
     w.dsp_b = wd.dsp_b;  // (the range apply reads which updates took the grid path)
-    launch_ds_decode(wd, e->side);
+    launch_ds_decode(wd, sw, e->side);
     HIPCHK(hipEventRecord(e->side_done, e->side));
   }
   if (sec_small) {
-    if (!sections_small(w, quick ? NONE : nsections, ch_key, ch_val, ch_slots - 1, s)) return fail(YCRDT_E_DEVICE, "small section pass refused");
+    if (!sections_small(w, sw, quick ? NONE : nsections, ch_key, ch_val, ch_slots - 1, s)) return fail(YCRDT_E_DEVICE, "small section pass refused");
     w.ch_key = ch_key;
     w.ch_val = ch_val;
     w.ch_mask = ch_slots - 1;
@@ -1265,10 +1253,10 @@ int run_decode(ycrdt_engine* e, ycrdt_batch* b, bool lazy, Decoded& D, bool gene
   if (quick) {
     launch_decode_tail_small(w, NONE, NONE, s);  // (the counts on the device)
     mark(e, "decode.clocks");
-  } else if (!lazy && decode_tail_small(w, nstructs, nsections, s)) {
+  } else if (!lazy && decode_tail_small(w, sw, nstructs, nsections, s)) {
     mark(e, "decode.clocks");  // (one workgroup: structs, clocks, client states, totals)
   } else {
-  launch_struct_decode(w, nstructs, s);
+  launch_struct_decode(w, sw, nstructs, s);
   mark(e, "decode.clocks");
   launch_struct_lenscan(w, nstructs, s);
   if (!lazy) {
@@ -1339,6 +1327,7 @@ int run_merge(ycrdt_engine* e, ycrdt_batch* b, const std::unordered_map<uint32_t
   hipStream_t s = e->stream;
   e->ws_owner = nullptr;
   b->packed = false;
+  const Switches& sw = b->sw;
   w.capped = 0;
   w.ncaps = 0;
   if (caps) {
@@ -1446,7 +1435,7 @@ int run_merge(ycrdt_engine* e, ycrdt_batch* b, const std::unordered_map<uint32_t
   {  // long delete-set runs spread over the grid (k_ds_tails; YCRDT_DS_TAILS=0: A/B); without the
      // buffer every run is flagged by the wavefront that met it
     bool okt = true;
-    w.ds_tails = D.ds_big && !env_off("YCRDT_DS_TAILS") ? take<uint4>(V, B_DSTAILS, DS_TAILS_CAP, okt) : nullptr;
+    w.ds_tails = D.ds_big && sw.ds_tails ? take<uint4>(V, B_DSTAILS, DS_TAILS_CAP, okt) : nullptr;
     if (!okt) w.ds_tails = nullptr;
   }
   if (U || nds) launch_units(w, nstructs, nclients, nds, U, D.ds_big, s);
@@ -1456,8 +1445,8 @@ int run_merge(ycrdt_engine* e, ycrdt_batch* b, const std::unordered_map<uint32_t
   // runs the integrate phases and the encode as two single-workgroup launches that read the
   // segment count on the device: no count synchronisation (a ~25 us round trip per merge), the
   // key table and output sized from the unit count (segments <= units)
-  const bool small = U && !sh && !D.array_roots && !D.any_rorigin && !D.nested && merge_small_fits(U) &&
-                     encode_small_fits(U, nclients) && (uint64_t)b->in_bytes + 48ull * U + 32ull * nclients + 64 <= (uint64_t(1) << 30);
+  const bool small = U && !sh && !D.array_roots && !D.any_rorigin && !D.nested && merge_small_fits(sw, U) &&
+                     encode_small_fits(sw, U, nclients) && (uint64_t)b->in_bytes + 48ull * U + 32ull * nclients + 64 <= (uint64_t(1) << 30);
   if (U && !small) {  // (a small merge cuts its segments in k_merge_small)
     launch_segments(w, nclients, U, s);
     rc = check(e, c, "segments");
@@ -1470,8 +1459,7 @@ int run_merge(ycrdt_engine* e, ycrdt_batch* b, const std::unordered_map<uint32_t
   // sized from those, not from every segment
   w.cap_keys = next_pow2(std::max<uint64_t>(2ull * std::min<uint64_t>(D.nroots, nseg_bound), 64));
   {  // test hook: keep only the low YCRDT_KEY_HASH_BITS bits of every list hash (collisions certain)
-    const int kb = getenv("YCRDT_KEY_HASH_BITS") ? atoi(getenv("YCRDT_KEY_HASH_BITS")) : 64;
-    w.key_mask = kb >= 1 && kb < 64 ? (1ull << kb) - 1 : ~0ull;
+    w.key_mask = sw.key_hash_bits < 64 ? (1ull << sw.key_hash_bits) - 1 : ~0ull;
   }
   w.k_hash = take<uint64_t>(V, B_KHASH, w.cap_keys, ok);
   w.k_rootmax = take<uint32_t>(V, B_KROOT, w.cap_keys, ok);
@@ -1507,7 +1495,7 @@ int run_merge(ycrdt_engine* e, ycrdt_batch* b, const std::unordered_map<uint32_t
   if (small) {
     // key table, segment properties, resolution, winners and merge flags (yc_merge.hip k_merge_small)
     mark(e, "merge.small");
-    launch_merge_small(w, NONE, U, s);
+    launch_merge_small(w, sw, NONE, U, s);
   } else if (nsegs) {
     mark(e, "merge.segment_fill");
     launch_segment_props_fill(w, nsegs, s);
@@ -1559,7 +1547,7 @@ int run_merge(ycrdt_engine* e, ycrdt_batch* b, const std::unordered_map<uint32_t
       mark(e, "merge.dead_types");
       if (D.nested) run_dead_keys(w, nsegs, s);  // only lists under a parent item can die with it
       mark(e, "merge.yata");
-      e->nlists = launch_yata(w, nsegs, narray, nclients, s, e->side, e->side_fork, e->side_done);
+      e->nlists = launch_yata(w, sw, nsegs, narray, nclients, s, e->side, e->side_fork, e->side_done);
       if (nmapx) launch_mapx_fix(w, nsegs, s);
       if (w.dbg && e->nlists) {
         unsigned long long h[7];
@@ -1607,7 +1595,7 @@ int run_merge(ycrdt_engine* e, ycrdt_batch* b, const std::unordered_map<uint32_t
   uint8_t* tmp2 = take<uint8_t>(V, B_TMP2, prim_tmp_bytes(nseg_bound + 2, 0), ok);
   if (!ok) return fail(YCRDT_E_DEVICE, oom("scan space"));
   mark(e, "encode.runs");
-  if (small || (!exact_out && encode_small_fits(nsegs, nclients))) {
+  if (small || (!exact_out && encode_small_fits(sw, nsegs, nclients))) {
     launch_encode_small(w, small ? NONE : nsegs, nclients, s);  // (the whole encode, one workgroup)
     mark(e, "end");
   } else {
@@ -1709,11 +1697,11 @@ int run_view(ycrdt_engine* e, ycrdt_batch* b, HostView& hv) {
   hv.segs.clear();
   hv.bytes.assign(b->nbytes, 0);
   if (nsegs) {
-    launch_view(w, vb, nsegs, nlists, narr, s);
+    launch_view(w, b->sw, vb, nsegs, nlists, narr, s);
     // a small view (the per-op path's doc) comes back in ONE synchronisation: counters, key count,
     // the key table up to its capacity, the list segments and the state bytes, queued together
     // (each synchronous copy cost a ~25 us round trip); a large one sizes the key copy first
-    static const bool big_only = env_on("YCRDT_VIEW_SYNC");
+    const bool big_only = process_switches().view_sync;
     const bool small = !big_only && (uint64_t)ck * sizeof(ViewKey) <= (256u << 10);
     Counters c;
     uint32_t nkeys = 0;
@@ -2069,9 +2057,8 @@ int pack_docs(ycrdt_engine* e, ycrdt_batch* b) {
 
 // HBM → host memory through the engine's pinned staging: a wave of chunks is copied D2H into one
 // half while worker threads move the previous wave out of the other half.
-int d2h_span(ycrdt_engine* e, uint8_t* host, const uint8_t* dev, uint64_t span) {
+int d2h_span(ycrdt_engine* e, uint64_t PIN_CHUNK, uint8_t* host, const uint8_t* dev, uint64_t span) {
   if (!span) return YCRDT_OK;
-  const uint64_t PIN_CHUNK = pin_chunk();
   const uint64_t nch = (span + PIN_CHUNK - 1) / PIN_CHUNK;
   const bool waves = nch > PIN_PER;
   Pinned& pin = e->pin_out;
@@ -2167,7 +2154,7 @@ int run_lazy_groups(ycrdt_engine* e, ycrdt_batch* b, uint8_t** dst, std::vector<
   HIPCHK(hipEventRecord(e->ev1, s));
   uint8_t* o = (uint8_t*)malloc(total ? total : 1);
   if (!o) return fail(YCRDT_E_CAPACITY, "host allocation failed");
-  rc = d2h_span(e, o, w.out, total);
+  rc = d2h_span(e, b->sw.pin_chunk, o, w.out, total);
   if (rc == YCRDT_OK) rc = check(e, c, "lazy write (groups)");
   if (rc) { free(o); return rc; }
   collect_phase_ms(e);
@@ -2182,7 +2169,7 @@ int split_docs(ycrdt_engine* e, ycrdt_batch* b, ycrdt_out* outs, ycrdt_out* svs)
   if (const int rc = pack_docs(e, b)) return rc;
   const std::vector<uint64_t>& offs = b->pack_offs;
   std::vector<uint8_t> all(offs.back());
-  if (const int rc = d2h_span(e, all.data(), (const uint8_t*)e->bufs[B_PACK].p, all.size())) return rc;
+  if (const int rc = d2h_span(e, b->sw.pin_chunk, all.data(), (const uint8_t*)e->bufs[B_PACK].p, all.size())) return rc;
   for (uint32_t d = 0; d < b->ndocs; ++d) {
     const uint64_t a = offs[2 * d], m = offs[2 * d + 1], z = offs[2 * d + 2];
     outs[d].ptr = (uint8_t*)malloc(m - a);
@@ -2232,7 +2219,7 @@ int ycrdt_engine_create(int device, int compat, ycrdt_engine** out) {
   auto* e = new ycrdt_engine();
   e->device = device;
   e->compat = compat == 135 ? 135 : 136;
-  e->debug_sync = env_on("YCRDT_DEBUG_SYNC");
+  e->debug_sync = read_switches().debug_sync;
   if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) { delete e; return fail(YCRDT_E_DEVICE, "stream"); }
   if (hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking) != hipSuccess) { delete e; return fail(YCRDT_E_DEVICE, "stream"); }
   hipEventCreateWithFlags(&e->side_done, hipEventDisableTiming);
@@ -2355,12 +2342,6 @@ namespace {
 
 constexpr size_t QUEUE_FLUSH_BYTES = size_t(1) << 30;  // deferred updates past this are merged at once
 
-// YCRDT_PREDECODE: 0 off, "check" decode the state the usual way and compare with its marks
-int predecode_mode() {
-  const char* v = getenv("YCRDT_PREDECODE");
-  return v && v[0] == '0' ? 0 : v && !strcmp(v, "check") ? 2 : 1;
-}
-
 // the marks block at p (yc_engine_host.h marks_layout: the one definition of its byte layout)
 static_assert(sizeof(Section) == 32, "tests/test_engine_host.py checks the marks layout with this size");
 PreMarks pre_marks(void* p, uint32_t nw, uint32_t cap) {
@@ -2378,21 +2359,21 @@ PreMarks pre_marks(void* p, uint32_t nw, uint32_t cap) {
 // the marks describe the doc's current state
 bool marked(const ycrdt_doc* d) { return d->marks.p && d->marks_len == d->state_len && d->marks_cap > 0; }
 // the doc's state goes into the next batch as source 0: decoded from its marks when they describe it
+// (YCRDT_PREDECODE: layout keeps the offer, drops it (0), or has the state decoded both ways (check))
 void doc_pre(ycrdt_doc* d, ycrdt_batch& b) {
   b.pre_src = -1;
   b.pre_check = false;
-  const int mode = predecode_mode();
-  if (!mode || !d->state_len || d->marks_len != d->state_len || !d->marks.p) return;
+  if (!d->state_len || d->marks_len != d->state_len || !d->marks.p) return;
   b.pre = pre_marks(d->marks.p, d->marks_nw, d->marks_cap);
   b.pre_src = 0;
-  b.pre_check = mode == 2;
 }
 
-// after a successful merge of the doc (the workspace holds its encode): the marks of the new state
-void doc_marks(ycrdt_doc* d) {
+// after a successful merge of the doc by a batch under the switches sw (the workspace holds its
+// encode): the marks of the new state
+void doc_marks(ycrdt_doc* d, const Switches& sw) {
   ycrdt_engine* e = d->e;
   d->marks_len = 0;
-  if (!predecode_mode() || !e->out_bytes || e->out_bytes >= (uint64_t(1) << 31)) return;
+  if (sw.predecode == Predecode::OFF || !e->out_bytes || e->out_bytes >= (uint64_t(1) << 31)) return;
   // (exactly the state's own 64-byte slot: the next staged update's words follow it)
   const uint32_t nw = (uint32_t)((e->out_bytes + 63) / 64), cap = (uint32_t)e->last.clients + 1;
   const size_t bytes = marks_layout(nw, cap, sizeof(Section)).bytes;
@@ -2439,7 +2420,7 @@ int commit_merge(ycrdt_doc* d, const std::vector<ycrdt_buf>& extra, const ClockM
     folded = true;
     return YCRDT_OK;
   };
-  static const bool nofold = env_on("YCRDT_NO_FOLD");  // (A/B)
+  const bool nofold = process_switches().no_fold;  // (A/B)
   if (rc == YCRDT_OK) {
     e->before_final = nofold ? nullptr : &fold;
     rc = run_merge(e, &b, nullptr, caps, order);
@@ -2479,7 +2460,7 @@ int commit_merge(ycrdt_doc* d, const std::vector<ycrdt_buf>& extra, const ClockM
   d->view.valid = false;
   // the new state's decode, from this encode (queued on the stream). Only now that the doc holds the
   // state: a failure above leaves the doc its old state AND the marks that describe it
-  doc_marks(d);
+  doc_marks(d, b.sw);
   e->ws_owner = d;  // the workspace now holds this doc's merged store (ensure_view reuses it)
   // a doc that is read through its view (local ops, toJSON, get) takes the view now, while the
   // workspace holds its merge: another doc's merge in between would otherwise force a re-merge
@@ -2726,10 +2707,6 @@ int flush_queued(ycrdt_engine* e, ycrdt_doc* const* docs, size_t n) {
   return flush_multi(e, q);
 }
 
-// Resident state bytes merged per device pass (one 4 GiB window holds them), and the state from
-// which a document is too large for the device path of these calls.
-constexpr uint64_t JSON_PASS_BYTES = uint64_t(1) << 31;
-
 // The path a document takes through such a call: the device pass, the fixed answer of an empty
 // document, or the single calls — when the call's switch is off, the document has pending structs or
 // a pending delete set, the engine mirrors Yjs 13.5, or the state is too large.
@@ -2894,7 +2871,7 @@ int ycrdt_docs_states_packed(ycrdt_engine* e, ycrdt_doc* const* docs, size_t n, 
     HIPCHK(hipMemcpyAsync(dpc, pc.data(), sizeof(Piece) * pc.size(), hipMemcpyHostToDevice, e->stream));
     copy_pieces(dpc, (uint32_t)pc.size(), e->stream);
     std::vector<uint8_t> host(dev);
-    if (const int rc = d2h_span(e, host.data(), buf, dev)) return rc;
+    if (const int rc = d2h_span(e, read_switches().pin_chunk, host.data(), buf, dev)) return rc;
     e->ws_owner = nullptr;  // B_PACK held a batch's split
     for (size_t i = 0; i < n; ++i)
       if (at[i] != ~0ull) memcpy(dst + o[2 * i], host.data() + at[i], docs[i]->state_len);
@@ -2940,7 +2917,8 @@ int ycrdt_docs_diff(ycrdt_engine* e, ycrdt_doc* const* docs, const ycrdt_buf* sv
   HIPCHK(hipSetDevice(e->device));
   if (const int rc = flush_queued(e, docs, n)) return rc;
   // which path every pair takes
-  const bool off = env_off("YCRDT_SYNC");
+  const Switches sw = read_switches();  // this call's
+  const bool off = !sw.sync;
   std::vector<uint8_t> kind(n, K_SINGLE);
   size_t ndev = 0;
   for (size_t i = 0; i < n; ++i) {
@@ -3075,7 +3053,7 @@ int ycrdt_docs_diff(ycrdt_engine* e, ycrdt_doc* const* docs, const ycrdt_buf* sv
     A.np = np;
     A.nitems = (uint32_t)nitems;
     A.piece_max = PIECE_MAX;
-    A.dbg_bounds = env_on("YCRDT_DEBUG_BOUNDS") ? 1u : 0u;
+    A.dbg_bounds = sw.debug_bounds ? 1u : 0u;
     mark(e, "sync_walk");
     launch_sync_walk(A.docs, (const SyncWalk*)(up + u_walk), nwk, A.ctr, A.dbg_bounds, s);
     mark(e, "sync_plan");
@@ -3116,7 +3094,7 @@ int ycrdt_docs_diff(ycrdt_engine* e, ycrdt_doc* const* docs, const ycrdt_buf* sv
     // the copy-out (the counters of the write ride in front of it on the stream)
     SyncCtr c2{};
     int rc = hipMemcpyAsync(&c2, A.ctr, sizeof c2, hipMemcpyDeviceToHost, s) == hipSuccess ? YCRDT_OK : fail(YCRDT_E_DEVICE, "HIP error (sync replies)");
-    if (rc == YCRDT_OK) rc = d2h_span(e, dst, outb, total);
+    if (rc == YCRDT_OK) rc = d2h_span(e, sw.pin_chunk, dst, outb, total);
     if (rc == YCRDT_OK && hipStreamSynchronize(s) != hipSuccess) rc = fail(YCRDT_E_DEVICE, "HIP error (sync replies)");
     if (rc == YCRDT_OK && c2.err) rc = map_err(c2.err, "sync replies (write)");
     if (rc) { if (direct) free(dst); return rc; }
@@ -3251,7 +3229,7 @@ int json_front(ycrdt_engine* e, const std::vector<ycrdt_doc*>& dl, const std::ve
   HIPCHK(hipMemsetAsync(W + o_mbase, 0xFF, 8 * ck, s));
   HIPCHK(hipMemsetAsync(W + o_abase, 0xFF, 8 * ck, s));
   HIPCHK(hipMemsetAsync(W + o_inv, 0xFF, 4 * ck, s));
-  launch_view(w, vb, nsegs, nlists, narr, s);
+  launch_view(w, b.sw, vb, nsegs, nlists, narr, s);
   JsonArgs& A = F.A;
   A = JsonArgs{};
   A.bytes = (const uint8_t*)b.bytes.p;
@@ -3398,7 +3376,7 @@ int text_out(ycrdt_engine* e, const uint8_t* outb, uint64_t total, std::vector<u
   text.resize(total);
   if (total) {
     if (extra) HIPCHK(hipMemcpyAsync(extra, dev_extra, extra_bytes, hipMemcpyDeviceToHost, s));
-    if (const int rc = d2h_span(e, text.data(), outb, total)) return rc;
+    if (const int rc = d2h_span(e, scratch_batch(e).sw.pin_chunk, text.data(), outb, total)) return rc;  // (the pass's batch: json_front)
   }
   HIPCHK(hipStreamSynchronize(s));
   float ms = 0;
@@ -3480,7 +3458,8 @@ int ycrdt_docs_json(ycrdt_engine* e, ycrdt_doc* const* docs, const char* const* 
   HIPCHK(hipSetDevice(e->device));
   if (const int rc = flush_queued(e, docs, n)) return rc;
   // which path every request takes; the device path's distinct documents and triples
-  const bool off = env_off("YCRDT_DOCS_JSON");
+  const Switches sw = read_switches();  // this call's
+  const bool off = !sw.docs_json;
   std::vector<uint8_t> kind(n, K_SINGLE);
   std::vector<size_t> want_of(n, 0);
   std::unordered_map<const ycrdt_doc*, uint32_t> dix;
@@ -3508,7 +3487,7 @@ int ycrdt_docs_json(ycrdt_engine* e, ycrdt_doc* const* docs, const char* const* 
   // device passes: documents in call order, as many as one window holds
   if (!wants.empty()) {
     // (tests shrink a pass through YCRDT_DOCS_JSON_PASS_BYTES to run the several-pass path on a few documents)
-    const std::vector<size_t> cut = doc_windows(dlist, pass_bytes(getenv("YCRDT_DOCS_JSON_PASS_BYTES"), JSON_PASS_BYTES));
+    const std::vector<size_t> cut = doc_windows(dlist, sw.docs_json_pass_bytes);
     std::vector<std::vector<size_t>> by_doc(dlist.size());
     for (size_t k = 0; k < wants.size(); ++k) by_doc[wants[k].doc].push_back(k);
     for (size_t k = 0; k + 1 < cut.size(); ++k) {
@@ -3638,7 +3617,8 @@ int ycrdt_docs_cache(ycrdt_engine* e, ycrdt_doc* const* docs, size_t n, const ch
   HIPCHK(hipSetDevice(e->device));
   if (const int rc = flush_queued(e, docs, n)) return rc;
   // which path every document takes; the device path's distinct documents
-  const bool off = env_off("YCRDT_DOCS_CACHE");
+  const Switches sw = read_switches();  // this call's
+  const bool off = !sw.docs_cache;
   std::vector<uint8_t> kind(n, K_SINGLE);
   std::vector<size_t> want_of(n, 0);
   std::unordered_map<const ycrdt_doc*, uint32_t> dix;
@@ -3650,7 +3630,7 @@ int ycrdt_docs_cache(ycrdt_engine* e, ycrdt_doc* const* docs, size_t n, const ch
   std::vector<CacheWant> wants(dlist.size());
   // device passes: documents in call order, as many as one window holds (document j is want j)
   // (tests shrink a pass through YCRDT_DOCS_CACHE_PASS_BYTES, as YCRDT_DOCS_JSON_PASS_BYTES does)
-  const std::vector<size_t> cut = doc_windows(dlist, pass_bytes(getenv("YCRDT_DOCS_CACHE_PASS_BYTES"), JSON_PASS_BYTES));
+  const std::vector<size_t> cut = doc_windows(dlist, sw.docs_cache_pass_bytes);
   for (size_t k = 0; k + 1 < cut.size(); ++k) {
     const std::vector<ycrdt_doc*> dl(dlist.begin() + cut[k], dlist.begin() + cut[k + 1]);
     if (const int rc = cache_pass(e, dl, ix, wants, cut[k], S.roots, S.device_ms)) return rc;
@@ -3858,7 +3838,8 @@ int ycrdt_docs_read(ycrdt_engine* e, const ycrdt_read* reads, size_t n, ycrdt_ou
     if (const int rc = flush_queued(e, docs.data(), n)) return rc;
   }
   // which path every read takes; the device path's distinct documents and reads
-  const bool off = env_off("YCRDT_DOCS_READ");
+  const Switches sw = read_switches();  // this call's
+  const bool off = !sw.docs_read;
   std::vector<uint8_t> kind(n, K_SINGLE);
   std::vector<size_t> want_of(n, 0);
   std::unordered_map<const ycrdt_doc*, uint32_t> dix;
@@ -3905,7 +3886,7 @@ int ycrdt_docs_read(ycrdt_engine* e, const ycrdt_read* reads, size_t n, ycrdt_ou
   // device passes: documents in call order, as many as one window holds
   if (!wants.empty()) {
     // (tests shrink a pass through YCRDT_DOCS_READ_PASS_BYTES, as YCRDT_DOCS_JSON_PASS_BYTES does)
-    const std::vector<size_t> cut = doc_windows(dlist, pass_bytes(getenv("YCRDT_DOCS_READ_PASS_BYTES"), JSON_PASS_BYTES));
+    const std::vector<size_t> cut = doc_windows(dlist, sw.docs_read_pass_bytes);
     std::vector<std::vector<size_t>> by_doc(dlist.size());
     for (size_t k = 0; k < wants.size(); ++k) by_doc[wants[k].doc].push_back(k);
     for (size_t k = 0; k + 1 < cut.size(); ++k) {
@@ -4077,10 +4058,10 @@ int ycrdt_batch_result_docs_packed(ycrdt_batch* b, uint8_t* dst, uint64_t cap, u
   if (!dst) return YCRDT_OK;
   if (cap < o.back()) return fail(YCRDT_E_ARG, "destination smaller than the packed result");
   if (b->ndocs == 1) {
-    if (const int rc = d2h_span(e, dst, e->w.out, e->out_bytes)) return rc;
-    return d2h_span(e, dst + e->out_bytes, e->w.sv_out, e->sv_bytes);
+    if (const int rc = d2h_span(e, b->sw.pin_chunk, dst, e->w.out, e->out_bytes)) return rc;
+    return d2h_span(e, b->sw.pin_chunk, dst + e->out_bytes, e->w.sv_out, e->sv_bytes);
   }
-  return d2h_span(e, dst, (const uint8_t*)e->bufs[B_PACK].p, o.back());
+  return d2h_span(e, b->sw.pin_chunk, dst, (const uint8_t*)e->bufs[B_PACK].p, o.back());
 }
 int ycrdt_merge_docs(ycrdt_engine* e, const ycrdt_buf* ups, const uint32_t* doc_of, size_t n, uint32_t ndocs,
                      ycrdt_out* updates, ycrdt_out* svs) {
@@ -4391,7 +4372,7 @@ int ycrdt_updates_state_vectors(ycrdt_engine* e, const ycrdt_buf* ups, size_t n,
   if (total > A.out_cap) { offs[0] = 0; return fail(YCRDT_E_DEVICE, "internal: state vectors past their bound"); }
   uint8_t* dst = (uint8_t*)malloc(total ? total : 1);
   if (!dst) { offs[0] = 0; return fail(YCRDT_E_CAPACITY, "host allocation failed"); }
-  if ((rc = d2h_span(e, dst, A.out, total)) || hipStreamSynchronize(s) != hipSuccess) {
+  if ((rc = d2h_span(e, b.sw.pin_chunk, dst, A.out, total)) || hipStreamSynchronize(s) != hipSuccess) {
     free(dst);
     offs[0] = 0;
     return rc ? rc : fail(YCRDT_E_DEVICE, "HIP error (state vectors from updates)");
@@ -4438,7 +4419,7 @@ int ycrdt_merge_updates_groups(ycrdt_engine* e, const ycrdt_buf* ups, const uint
     for (size_t i = 0; i < n; ++i) members[cur[group_of[i]]++] = (uint32_t)i;
   }
   enum : uint8_t { K_COPIED = 0, K_SINGLE, K_DEV };
-  const bool all_single = e->compat == 135 || env_off("YCRDT_STORE");
+  const bool all_single = e->compat == 135 || !read_switches().store;  // (this call's)
   std::vector<uint8_t> kind(ngroups);
   std::vector<uint32_t> dev_of(ngroups, NONE);  // group -> its document in the staged batch
   uint32_t nd = 0;
@@ -4964,7 +4945,8 @@ int docs_write_call(ycrdt_engine* e, const ycrdt_write* ops, size_t n, ycrdt_out
     if (const int rc = flush_queued(e, docs.data(), n)) return rc;
   }
   // the call's documents and the path each takes: all ops of one document take the same one
-  const bool off = env_off(transact ? "YCRDT_DOCS_TRANSACT" : "YCRDT_DOCS_WRITE");
+  const Switches sw = read_switches();  // this call's
+  const bool off = !(transact ? sw.docs_transact : sw.docs_write);
   std::vector<uint8_t> bad(n, 0);
   for (size_t i = 0; i < n; ++i) bad[i] = write_args_bad(ops[i]) ? 1 : 0;
   std::unordered_map<const ycrdt_doc*, uint32_t> cix;
@@ -5030,7 +5012,7 @@ int docs_write_call(ycrdt_engine* e, const ycrdt_write* ops, size_t n, ycrdt_out
   if (!wants.empty()) {
     // (tests shrink a pass through YCRDT_DOCS_WRITE_PASS_BYTES, as YCRDT_DOCS_READ_PASS_BYTES does)
     const std::vector<size_t> cut =
-        doc_windows(dlist, pass_bytes(getenv(transact ? "YCRDT_DOCS_TRANSACT_PASS_BYTES" : "YCRDT_DOCS_WRITE_PASS_BYTES"), JSON_PASS_BYTES));
+        doc_windows(dlist, transact ? sw.docs_transact_pass_bytes : sw.docs_write_pass_bytes);
     for (size_t k = 0; k + 1 < cut.size(); ++k) {
       const std::vector<ycrdt_doc*> dl(dlist.begin() + cut[k], dlist.begin() + cut[k + 1]);
       const std::vector<size_t> ws = window_wants(by_doc, cut[k], cut[k + 1]);

@@ -87,6 +87,10 @@ inline MarksLayout marks_layout(uint32_t nw, uint32_t cap, size_t section_bytes)
 
 // ---- shared by the calls over many documents (ycrdt_docs_json / _cache / _read / _write / _diff)
 
+// Resident state bytes merged per device pass (one 4 GiB window holds them), and the state from
+// which a document is too large for the device path of these calls.
+constexpr uint64_t JSON_PASS_BYTES = uint64_t(1) << 31;
+
 // Resident state bytes merged per device pass: `cap`, or what the call's environment variable `env`
 // asks for (tests shrink a pass to run the several-pass path on a few documents): unset or 0 is the
 // cap, and no value exceeds it.

@@ -1096,13 +1096,12 @@ __global__ __launch_bounds__(MS_LANES) void k_merge_small(Work w, uint32_t nsegs
   __syncthreads();
   block_scan_u32<MS_LANES>(w.g_tmp, w.g_outid, nsegs + 1, part);
 }
-bool merge_small_fits(uint64_t nsegs_bound) {
-  const bool off = env_off("YCRDT_MERGE_SMALL");  // (read per merge: A/B in one process)
-  return !off && nsegs_bound && nsegs_bound <= MS_SMALL && (nsegs_bound + 63) / 64 <= SEG_SMALL_WORDS && encode_runs_small((uint32_t)nsegs_bound);
+bool merge_small_fits(const Switches& sw, uint64_t nsegs_bound) {
+  return sw.merge_small && nsegs_bound && nsegs_bound <= MS_SMALL && (nsegs_bound + 63) / 64 <= SEG_SMALL_WORDS && encode_runs_small((uint32_t)nsegs_bound);
 }
 // (nunits != 0: the segments too, nsegs read on the device)
-void launch_merge_small(const Work& w, uint32_t nsegs, uint64_t nunits, hipStream_t s) {
-  if (getenv("YCRDT_PHASE_FENCE") && getenv("YCRDT_PHASE_FENCE")[0] == '1')
+void launch_merge_small(const Work& w, const Switches& sw, uint32_t nsegs, uint64_t nunits, hipStream_t s) {
+  if (sw.phase_fence)
     hipLaunchKernelGGL(k_merge_small<true>, dim3(1), dim3(MS_LANES), 0, s, w, nsegs, nunits);
   else
     hipLaunchKernelGGL(k_merge_small<false>, dim3(1), dim3(MS_LANES), 0, s, w, nsegs, nunits);

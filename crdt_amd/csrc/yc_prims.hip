@@ -67,10 +67,7 @@ size_t prim_tmp_bytes(uint64_t scan_n, uint64_t sort_n) {
 // merge runs a dozen scans. Each lane sums a contiguous run, the 1 024 run sums are scanned in LDS,
 // each lane writes its run's prefixes; a lane reads in[i] before it writes out[i] and runs are
 // disjoint, so in == out is safe. Same results as rocprim::exclusive_scan (wrapping plus).
-static bool getenv_flag(const char* name) {  // experiments: YCRDT_ROCPRIM_SCAN=1 takes rocPRIM's scans
-  static const bool v = getenv(name) && getenv(name)[0] == '1';
-  return v;
-}
+static bool rocprim_scan() { return process_switches().rocprim_scan; }  // experiments: YCRDT_ROCPRIM_SCAN=1 takes rocPRIM's scans
 constexpr uint32_t SMALL_SCAN_LANES = 1024, SMALL_SCAN_MAX = SMALL_SCAN_LANES * 16;
 template <class T>
 __global__ __launch_bounds__(SMALL_SCAN_LANES) void k_scan_small(const uint32_t* in, T* out, uint32_t n) {
@@ -324,7 +321,7 @@ void scan_u32(void* tmp, size_t tmpb, const uint32_t* in, uint32_t* out, uint64_
     hipLaunchKernelGGL(k_scan_small<uint32_t>, dim3(1), dim3(SMALL_SCAN_LANES), 0, s, in, out, (uint32_t)n);
     return;
   }
-  if (!getenv_flag("YCRDT_ROCPRIM_SCAN") && scan_lb<uint32_t>(in, out, n, s)) return;
+  if (!rocprim_scan() && scan_lb<uint32_t>(in, out, n, s)) return;
   rocprim::exclusive_scan(tmp, tmpb, in, out, 0u, (size_t)n, rocprim::plus<uint32_t>(), s);
 }
 
@@ -334,7 +331,7 @@ void scan_u32_to_u64(void* tmp, size_t tmpb, const uint32_t* in, uint64_t* out, 
     hipLaunchKernelGGL(k_scan_small<uint64_t>, dim3(1), dim3(SMALL_SCAN_LANES), 0, s, in, out, (uint32_t)n);
     return;
   }
-  if (!getenv_flag("YCRDT_ROCPRIM_SCAN") && scan_lb<uint64_t>(in, out, n, s)) return;
+  if (!rocprim_scan() && scan_lb<uint64_t>(in, out, n, s)) return;
   rocprim::exclusive_scan(tmp, tmpb, in, out, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), s);
 }
 

@@ -183,8 +183,8 @@ __global__ void k_vseg_fill(Work w, uint32_t narr, const uint32_t* __restrict__ 
   fill_seg(w, order[p], false, segs[p]);
 }
 
-void launch_view(const Work& w, const ViewBufs& v, uint32_t nsegs, uint32_t nlists, uint32_t narr, hipStream_t s) {
-  if ((!nlists || !narr) && w.cap_keys <= VS_SMALL && nsegs <= VS_SMALL && !env_off("YCRDT_VIEW_SMALL")) {
+void launch_view(const Work& w, const Switches& sw, const ViewBufs& v, uint32_t nsegs, uint32_t nlists, uint32_t narr, hipStream_t s) {
+  if ((!nlists || !narr) && w.cap_keys <= VS_SMALL && nsegs <= VS_SMALL && sw.view_small) {
     hipLaunchKernelGGL(k_view_small, dim3(1), dim3(VS_LANES), 0, s, w, nsegs, v.kmap, v.krep, v.keys, v.nkeys);
     return;
   }

@@ -7,6 +7,7 @@
 #include <initializer_list>
 #include "yc_common.h"
 #include "yc_view.h"
+#include "yc_switches.h"
 
 namespace yc {
 
@@ -110,7 +111,7 @@ struct Work {
   const uint32_t* fwc_off = nullptr; // [nupd] record base of each record-mode update, NONE otherwise (null: none)
   uint32_t* rtab = nullptr;        // record mode: chain_len at every byte of those updates (k_rtab), indexed as fwc
   uint4* rk = nullptr;             // [nupd] record mode: the ranked last section (first struct, n, section, 1)
-  uint32_t scan_fused = 1;         // 0 (YCRDT_SCAN_FUSED=0, read per merge): the large batches' clocks, segment numbering
+  uint32_t scan_fused = 1;         // 0 (YCRDT_SCAN_FUSED=0, read when the batch is staged): the large batches' clocks, segment numbering
                                    // and bitmap prefixes as separate column + scan passes (A/B, tests)
   uint32_t dbg_bounds = 0;         // YCRDT_DEBUG_BOUNDS=1: table indexes of the unit passes and the single-workgroup
                                    // kernels checked against their tables' sizes (bounds_fail: a message + ERR_CAPACITY)
@@ -359,7 +360,7 @@ struct Work {
   uint8_t* o_gen = nullptr;        // [NO] 1: the general encoder takes the output struct (k_out_sizes_general)
   unsigned long long* o_rec = nullptr;  // [NO] encode record (yc_encrec.h) of the output structs the whole-item
                                    // encoder takes, 0 = none (k_out_sizes -> k_write_structs). Aliases g_hop.
-  uint32_t enc_record = 1;         // 0 (YCRDT_ENC_RECORD=0, read per merge; or a batch of several windows): no
+  uint32_t enc_record = 1;         // 0 (YCRDT_ENC_RECORD=0, read when the batch is staged; or a batch of several windows): no
                                    // valid record is written, every struct is encoded from its columns
   uint32_t* r_seg = nullptr;       // [runs] first segment of delete-set run
   uint32_t* r_len = nullptr;       // [runs] run length in units
@@ -758,7 +759,7 @@ struct ViewBufs {
   uint32_t* order = nullptr; // [narr] members in document order
   ViewSeg* segs = nullptr;   // [narr]
 };
-void launch_view(const Work& w, const ViewBufs& v, uint32_t nsegs, uint32_t nlists, uint32_t narr, hipStream_t s);
+void launch_view(const Work& w, const Switches& sw, const ViewBufs& v, uint32_t nsegs, uint32_t nlists, uint32_t narr, hipStream_t s);
 
 // ---- a doc state's decode, written by the encode that produced it (k_state_marks): the next merge
 // of the doc takes its state's struct / section starts, section records and delete-set start from
@@ -777,28 +778,29 @@ void launch_state_marks(const Work& w, uint32_t nout, uint32_t nclients, const P
 // decoded the usual way too)
 void launch_predecoded(const Work& w, uint32_t u, const PreMarks& m, bool check, hipStream_t s);
 
-// ---- launch entry points (yc_decode.hip / yc_merge.hip / yc_encode.hip / yc_prims.hip)
-void launch_chunks(const Work& w, hipStream_t s);  // k_spec + k_walk: large updates
-void launch_direct(const Work& w, hipStream_t s);  // k_direct: small updates
-bool wave_decode(const Work& w);                  // few small updates: k_wlen + k_wrank (else k_direct)
+// ---- launch entry points (yc_decode.hip / yc_merge.hip / yc_encode.hip / yc_prims.hip); sw: the
+// batch's switches (yc_switches.h), for the entry points that choose a path on the host
+void launch_chunks(const Work& w, const Switches& sw, hipStream_t s);  // k_spec + k_walk: large updates
+void launch_direct(const Work& w, const Switches& sw, hipStream_t s);  // k_direct: small updates
+bool wave_decode(const Work& w, const Switches& sw);  // few small updates: k_wlen + k_wrank (else k_direct)
 void launch_client_hash(const Work& w, uint64_t* key, uint32_t* val, uint32_t mask, hipStream_t s);
-bool sections_small(const Work& w, uint32_t nsections, uint64_t* key, uint32_t* val, uint32_t mask, hipStream_t s);  // ranks + client table + hash, one workgroup
+bool sections_small(const Work& w, const Switches& sw, uint32_t nsections, uint64_t* key, uint32_t* val, uint32_t mask, hipStream_t s);  // ranks + client table + hash, one workgroup
 void launch_struct_count(const Work& w, hipStream_t s);
 // wcnt / wsec: the popcount prefixes of two bitmaps of nwords words (nwords + 1 entries each) in one
 // look-back launch; false: no look-back states (the caller takes the separate passes)
 bool popc_scan2(const uint64_t* b0, uint32_t* o0, const uint64_t* b1, uint32_t* o1, uint32_t nwords, hipStream_t s);
 void launch_struct_scatter(const Work& w, hipStream_t s);
 void launch_ds_bound(const Work& w, hipStream_t s);
-bool count_ds_small(const Work& w, hipStream_t s);  // counts + delete-set bounds in one workgroup (small batches)
-void launch_ds_decode(const Work& w, hipStream_t s);
+bool count_ds_small(const Work& w, const Switches& sw, hipStream_t s);  // counts + delete-set bounds in one workgroup (small batches)
+void launch_ds_decode(const Work& w, const Switches& sw, hipStream_t s);
 void launch_section_clients(const Work& w, uint32_t nsections, hipStream_t s);
 void launch_client_table(Work& w, uint32_t nsections, hipStream_t s);
-void launch_struct_decode(const Work& w, uint32_t nstructs, hipStream_t s);
+void launch_struct_decode(const Work& w, const Switches& sw, uint32_t nstructs, hipStream_t s);
 void launch_struct_lenscan(const Work& w, uint32_t nstructs, hipStream_t s);
 constexpr uint32_t DT_SMALL = 4096;  // structs of the one-workgroup decode tail (k_decode_tail_small)
 // the clocks without a length scan (k_struct_clock_lb): batches past DT_SMALL structs unless YCRDT_SCAN_FUSED=0
 inline bool clocks_fused(const Work& w, uint32_t nstructs) { return w.scan_fused && nstructs > DT_SMALL; }
-bool decode_tail_small(const Work& w, uint32_t nstructs, uint32_t nsections, hipStream_t s);
+bool decode_tail_small(const Work& w, const Switches& sw, uint32_t nstructs, uint32_t nsections, hipStream_t s);
 void launch_decode_tail_small(const Work& w, uint32_t nstructs, uint32_t nsections, hipStream_t s);  // NONE: counts on the device  // one workgroup: structs .. client states (small, integrate)
 void launch_json_structs(const Work& w, uint32_t nstructs, hipStream_t s);  // JSON.parse of JSON-like contents
 // JSON.stringify(JSON.parse(.)) of the listed structs' contents (k_json_canon): one lane per struct,
@@ -826,8 +828,8 @@ uint32_t run_key_resolution(const Work& w, uint32_t nsegs, hipStream_t s);
 uint32_t run_descent(const Work& w, uint32_t nsegs, hipStream_t s, bool fold_overwrite);
 void launch_mapx_flip(const Work& w, uint32_t nsegs, hipStream_t s);  // full-YATA map entries -> the YATA kernels
 void launch_mapx_fix(const Work& w, uint32_t nsegs, hipStream_t s);   // ... and back: the last one wins
-bool merge_small_fits(uint64_t nsegs_bound);  // map-only small merges: one workgroup (k_merge_small)
-void launch_merge_small(const Work& w, uint32_t nsegs, uint64_t nunits, hipStream_t s);  // nunits != 0: segments too, nsegs on the device
+bool merge_small_fits(const Switches& sw, uint64_t nsegs_bound);  // map-only small merges: one workgroup (k_merge_small)
+void launch_merge_small(const Work& w, const Switches& sw, uint32_t nsegs, uint64_t nunits, hipStream_t s);  // nunits != 0: segments too, nsegs on the device
 bool launch_merge_flags(const Work& w, uint32_t nsegs, hipStream_t s, bool fold_overwrite);  // true: run ids scanned too
 bool encode_runs_small(uint32_t nsegs);  // the one-workgroup delete-set runs (k_runs_small)
 void launch_merge_flags_only(const Work& w, uint32_t nsegs, hipStream_t s, bool fold_overwrite);
@@ -843,7 +845,7 @@ constexpr uint32_t DSP_MAXBLK = 8192;  // client blocks of one delete set decode
 constexpr uint32_t DSH_STRIDE = 32, DSH_SEG = DSP_MAXBLK / DSH_STRIDE;  // header jumps (yc_decode.hip k_dsh_*)
 constexpr uint32_t DSH_MIN_BLOCKS = 32;  // delete sets of more client blocks take the jumps
 constexpr uint32_t LISTS_UNNUMBERED = 0xFFFFFFFFu;  // launch_yata: lists exist, launch_ylists numbers them
-uint32_t launch_yata(const Work& w, uint32_t nsegs, uint32_t narray, uint32_t nclients, hipStream_t s, hipStream_t side,
+uint32_t launch_yata(const Work& w, const Switches& sw, uint32_t nsegs, uint32_t narray, uint32_t nclients, hipStream_t s, hipStream_t side,
                      hipEvent_t ev_fork, hipEvent_t ev_join);
 uint32_t launch_ylists(const Work& w, uint32_t nsegs, hipStream_t s);
 
@@ -854,7 +856,7 @@ void launch_out_sizes(const Work& w, uint32_t nsegs, uint32_t nclients, hipStrea
 void launch_encode_layout(const Work& w, uint32_t nsegs, uint32_t nclients, hipStream_t s, hipEvent_t ev_join);
 void launch_encode_write(const Work& w, uint32_t nsegs, uint32_t nclients, hipStream_t s);
 void launch_write_structs(const Work& w, uint32_t nsegs, uint32_t nclients, hipStream_t s);
-bool encode_small_fits(uint64_t nsegs_bound, uint32_t nclients);  // the whole encode, one workgroup (small batches)
+bool encode_small_fits(const Switches& sw, uint64_t nsegs_bound, uint32_t nclients);  // the whole encode, one workgroup (small batches)
 void launch_encode_small(const Work& w, uint32_t nsegs, uint32_t nclients, hipStream_t s);  // nsegs NONE: read on the device
 
 // rocPRIM wrappers (yc_prims.hip)

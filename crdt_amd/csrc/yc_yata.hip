@@ -1231,15 +1231,14 @@ uint32_t launch_ylists(const Work& w, uint32_t nsegs, hipStream_t s) {
 
 // Returns the list count, or LISTS_UNNUMBERED when the tree path ran without numbering them
 // (launch_ylists, when a view asks).
-uint32_t launch_yata(const Work& w, uint32_t nsegs, uint32_t narray, uint32_t nclients, hipStream_t s, hipStream_t side,
+uint32_t launch_yata(const Work& w, const Switches& sw, uint32_t nsegs, uint32_t narray, uint32_t nclients, hipStream_t s, hipStream_t side,
                      hipEvent_t ev_fork, hipEvent_t ev_join) {
   if (!nsegs) return 0;
   if (!narray) return 0;  // g_right is only read for YArray members (merge predicate, view)
   hipLaunchKernelGGL(k_yinit, dim3(nsegs / 256 + 1), dim3(256), 0, s, w, nsegs);
-  static const bool seq = getenv("YCRDT_YATA") && !strcmp(getenv("YCRDT_YATA"), "seq");
-  if (!seq && (uint64_t)nsegs * 5 < 0xFFFFFFF0ull) {  // sibling keys NS + list slot stay below NONE
-    static const bool eager = getenv("YCRDT_YLISTS_EAGER") && getenv("YCRDT_YLISTS_EAGER")[0] == '1';
-    const uint32_t nl = eager ? launch_ylists(w, nsegs, s) : LISTS_UNNUMBERED;
+  const Switches& ps = process_switches();  // (YCRDT_YATA, YCRDT_YLISTS_EAGER: once per process)
+  if (ps.yata != YataMode::SEQ && (uint64_t)nsegs * 5 < 0xFFFFFFF0ull) {  // sibling keys NS + list slot stay below NONE
+    const uint32_t nl = ps.ylists_eager ? launch_ylists(w, nsegs, s) : LISTS_UNNUMBERED;
     launch_yata_tree(w, nsegs, s, side, ev_fork, ev_join);
     return nl;
   }
@@ -1247,7 +1246,7 @@ uint32_t launch_yata(const Work& w, uint32_t nsegs, uint32_t narray, uint32_t nc
   if (!nlists) return 0;
   hipMemsetAsync(w.y_before, 0, sizeof(uint32_t) * (nsegs + 1), s);  // stamps: 0 is never issued
   hipMemsetAsync(w.y_confl, 0, sizeof(uint32_t) * (nsegs + 1), s);
-  if (nclients < 16384 && !getenv("YCRDT_YATA_GLOBAL")) {  // client index in 14 bits
+  if (nclients < 16384 && !sw.yata_global) {  // client index in 14 bits
     hipLaunchKernelGGL(k_yata_lds<YL_SMALL>, dim3(nlists), dim3(64), 0, s, w, nlists, 1u);
     hipLaunchKernelGGL(k_yata_lds<YL_LARGE>, dim3(nlists), dim3(256), 0, s, w, nlists, YL_SMALL + 1);
     hipLaunchKernelGGL(k_yata, dim3(nlists), dim3(64), 0, s, w, nlists, YL_LARGE + 1);

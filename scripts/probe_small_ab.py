@@ -1,5 +1,5 @@
 """Per-op loop (bench.py per_op_leg) with the single-workgroup small-batch kernels on / off,
-alternated in ONE process (the switches are read per merge): ops/s per mode and round."""
+alternated in ONE process (the switches are read when the batch is staged): ops/s per mode and round."""
 import os
 import sys
 

@@ -32,7 +32,7 @@ ME = 0x7FFFFFF0
 @pytest.fixture(params=["default", "grid", "collide", "grid_collide"])
 def path(request, monkeypatch):
     """The single-workgroup merge or the grid kernels, every list in its own hash value or all of
-    them in 16 (both switches are read per merge)."""
+    them in 16 (both switches are read when the batch is staged)."""
     monkeypatch.delenv("YCRDT_MERGE_SMALL", raising=False)
     monkeypatch.delenv("YCRDT_KEY_HASH_BITS", raising=False)
     if "grid" in request.param:

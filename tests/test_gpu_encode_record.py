@@ -27,7 +27,7 @@ def path(request, monkeypatch):
     for k in ("YCRDT_MERGE_SMALL", "YCRDT_ENCODE_SMALL", "YCRDT_ENC_RECORD", "YCRDT_WIN_SHIFT"):
         monkeypatch.delenv(k, raising=False)
     if request.param == "grid":
-        monkeypatch.setenv("YCRDT_MERGE_SMALL", "0")  # read per merge
+        monkeypatch.setenv("YCRDT_MERGE_SMALL", "0")  # read when the batch is staged
         monkeypatch.setenv("YCRDT_ENCODE_SMALL", "0")
     return request.param
 
@@ -191,7 +191,7 @@ def _docs_case():
 
 
 def _both_settings(monkeypatch, run):
-    """run() with YCRDT_ENC_RECORD unset and =0 (read per merge): (with records, without)."""
+    """run() with YCRDT_ENC_RECORD unset and =0 (read when the batch is staged): (with records, without)."""
     monkeypatch.delenv("YCRDT_ENC_RECORD", raising=False)
     on = run()
     monkeypatch.setenv("YCRDT_ENC_RECORD", "0")

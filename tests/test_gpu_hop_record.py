@@ -22,7 +22,7 @@ PATHS = ["default", "grid"]
 @pytest.fixture(params=PATHS)
 def path(request, monkeypatch):
     if request.param == "grid":
-        monkeypatch.setenv("YCRDT_MERGE_SMALL", "0")  # read per merge (merge_small_fits)
+        monkeypatch.setenv("YCRDT_MERGE_SMALL", "0")  # read when the batch is staged (merge_small_fits)
     else:
         monkeypatch.delenv("YCRDT_MERGE_SMALL", raising=False)
     return request.param
@@ -30,7 +30,7 @@ def path(request, monkeypatch):
 
 @pytest.fixture
 def collide(monkeypatch):
-    monkeypatch.setenv("YCRDT_KEY_HASH_BITS", "4")  # read per merge: every list in <= 16 hash values
+    monkeypatch.setenv("YCRDT_KEY_HASH_BITS", "4")  # read when the batch is staged: every list in <= 16 hash values
     yield
 
 

@@ -119,7 +119,7 @@ def _truncated_any():
 def gpu_results():
     """name -> bytes of every case, under whatever YCRDT_SD_GROUP the process runs with."""
     before = os.environ.get("YCRDT_DECODE_SMALL")
-    os.environ["YCRDT_DECODE_SMALL"] = "0"  # (read per merge)
+    os.environ["YCRDT_DECODE_SMALL"] = "0"  # (read when the batch is staged)
     try:
         return _gpu_results()
     finally:
