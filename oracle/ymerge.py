@@ -131,6 +131,15 @@ def utf16_slice(b, off):
     return b""
 
 
+def utf16_splice(b, off):
+    """ContentString.splice(off) (Y@69588), the right part: between the two units of a surrogate pair
+    the low half becomes U+FFFD (the left part, which the lazy merge drops, gets one too)."""
+    try:
+        return utf16_slice(b, off)
+    except ValueError:
+        return "�".encode("utf-8") + utf16_slice(b, off + 1)
+
+
 # ---------------------------------------------------------------------------- structs
 GC, SKIP, ITEM = 0, 10, 1
 
@@ -318,7 +327,7 @@ def slice_struct(s, e):
     elif s.ref in (2, 8):
         nc = c[e:]
     elif s.ref == 4:
-        nc = utf16_slice(c, e)
+        nc = utf16_splice(c, e)
     else:
         raise ValueError("splice of a length-1 content")
     return Struct(ITEM, s.client, s.clock + e, s.length - e, s.ref, (s.client, s.clock + e - 1), s.right_origin,

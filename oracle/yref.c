@@ -452,6 +452,7 @@ static uint32_t get_state(yo_doc *d, uint32_t client) {
 static int64_t find_index(client_structs *c, uint32_t clock) {
   if (!c || c->n == 0) return -1;
   int64_t lo = 0, hi = (int64_t)c->n - 1;
+  if (c->s[hi]->id.clock == clock) return hi; /* findIndexSS tries the last struct first (an empty one is found only so) */
   while (lo <= hi) {
     int64_t mid = (lo + hi) / 2;
     ys *s = c->s[mid];
@@ -1458,6 +1459,7 @@ int yo_encode_state_as_update(yo_doc *d, const uint8_t *sv, size_t svlen, uint8_
     if (!sv_get(&target, cur.e[i].client, &x)) sv_set(&sm, cur.e[i].client, 0);
   }
   bvu(&b, sm.n);
+  int lone = 0;
   cc_t *e = xmalloc(sizeof(cc_t) * (sm.n + 1));
   for (uint32_t i = 0; i < sm.n; i++) { e[i].client = sm.e[i].client; e[i].clock = sm.e[i].clock; }
   qsort(e, sm.n, sizeof(cc_t), cmp_cc_desc);
@@ -1469,6 +1471,15 @@ int yo_encode_state_as_update(yo_doc *d, const uint8_t *sv, size_t svlen, uint8_
     bvu(&b, c->n - (uint32_t)st);
     bvu(&b, e[i].client);
     bvu(&b, clock);
+    {
+      /* Item.write at an offset between the two units of a surrogate pair: writeVarString of a lone
+       * low surrogate, encodeURIComponent throws URIError (lib0 0.2.42) */
+      const ys *f = c->s[st];
+      uint32_t off = clock - f->id.clock;
+      if (off > 0 && f->kind == K_ITEM && f->c.ref == CT_STRING && off < f->c.nu16 && f->c.u16[off] >= 0xDC00 &&
+          f->c.u16[off] <= 0xDFFF && f->c.u16[off - 1] >= 0xD800 && f->c.u16[off - 1] <= 0xDBFF)
+        lone = 1;
+    }
     write_struct(&b, d, c->s[st], clock - c->s[st]->id.clock);
     for (uint32_t k = (uint32_t)st + 1; k < c->n; k++) write_struct(&b, d, c->s[k], 0);
   }
@@ -1508,6 +1519,11 @@ int yo_encode_state_as_update(yo_doc *d, const uint8_t *sv, size_t svlen, uint8_
   free(sm.e);
   free(cur.e);
   free(target.e);
+  if (lone) {
+    free(b.p);
+    set_err("URI malformed");
+    return YO_E_DECODE;
+  }
   *out = b.p;
   *outlen = b.n;
   return YO_OK;
