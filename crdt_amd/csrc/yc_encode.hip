@@ -214,10 +214,17 @@ __device__ __forceinline__ uint32_t encode_struct_general(const Work& w, uint32_
           else nbytes += nb;
           continue;
         }
+        // a segment edge inside a surrogate pair is a split Yjs made: U+FFFD on both sides (str_copy);
+        // the offset of a delta encode strictly inside a segment is where Yjs writes, and throws
         uint32_t b0 = 0, b1 = 0;
-        if (!content_slice(w, sr, u0 - sb, u1 - sb, b0, b1)) { raise_err(&w.ctr->err, ERR_UNSUPPORTED); return size; }
-        if (pass == 1) p = copy_bytes(out, p, struct_bytes(w, sr) + b0, b1 - b0);
-        else nbytes += b1 - b0;
+        if (!content_slice(w, sr, u0 - sb, u1 - sb, b0, b1, u0 > (uint32_t)(seg_start(w, s) - base))) {
+          raise_err(&w.ctr->err, ERR_UNSUPPORTED);
+          if (ref == REF_STRING) w.ctr->err_info = ERRI_PAIR_OFFSET;
+          return size;
+        }
+        if (pass == 0) nbytes += b1 - b0;
+        else if (ref == REF_STRING) p = str_copy(out, p, struct_bytes(w, sr) + b0, b1 - b0);
+        else p = copy_bytes(out, p, struct_bytes(w, sr) + b0, b1 - b0);
       }
     }
     size += (ref == REF_STRING ? vu_size(nbytes) : vu_size(len - off)) + nbytes;

@@ -706,6 +706,9 @@ int check(ycrdt_engine* e, Counters& c, const char* where) {
     const uint32_t k = c.err_info & 0xFFFFu;
     return fail(YCRDT_E_CAPACITY, std::string("bounds check (YCRDT_DEBUG_BOUNDS): an index past its table: ") + what[k < 8 ? k : 0] + " at " + where);
   }
+  if (c.err == ERR_UNSUPPORTED && c.err_info == ERRI_PAIR_OFFSET)
+    return fail(YCRDT_E_UNSUPPORTED, std::string("Yjs throws at this offset: the state vector's clock falls between the two units of a surrogate "
+                                                 "pair of a string (lib0's writeVarString: URIError) at ") + where);
   if (c.err) return map_err(c.err, where);
   return YCRDT_OK;
 }

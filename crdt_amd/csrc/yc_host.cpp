@@ -50,7 +50,7 @@ struct JsonCtx {
 
 void type_json(JsonCtx& c, uint32_t parent_unit, uint32_t type_ref, const ViewKey* array_list, std::string& o);
 
-SegCursor cursor(const HostView& v, const ViewSeg& s, bool entry) { return SegCursor(v.bytes.data(), s.b0, s.b1, s.ref, s.len, entry); }
+SegCursor cursor(const HostView& v, const ViewSeg& s, bool entry) { return SegCursor(v.bytes.data(), s.b0, s.b1, s.ref, s.len, entry, (s.flags >> VS_HALF_SHIFT) & 3u); }
 
 // The next element of segment `s` appended to `o`: 0 none left, 1 written, 2 `undefined` (nothing
 // written) — the states of view_map_get / view_array_get. Content that is truncated inside its
@@ -143,15 +143,15 @@ void array_json(JsonCtx& c, const ViewKey* L, std::string& o) {  // typeListToAr
 }
 
 void text_json(JsonCtx& c, const ViewKey* L, std::string& o) {  // YText.toJSON: the visible string
-  std::string s;
+  JString w{o};
+  o.push_back('"');
   if (L)
     for (uint32_t i = 0; i < L->nseg; ++i) {
       const ViewSeg& g = c.v.segs[L->seg0 + i];
       if ((g.flags & VS_DELETED) || !(g.flags & VS_ITEM) || g.ref != REF_STRING) continue;
-      s.append((const char*)c.v.bytes.data() + g.b0, g.b1 - g.b0);
+      json_put_piece(w, c.v.bytes.data() + g.b0, g.b1 - g.b0, (g.flags >> VS_HALF_SHIFT) & 3u);  // (piece by piece: a half pair is U+FFFD)
     }
-  JString w{o};
-  json_put_str(w, (const uint8_t*)s.data(), s.size());
+  o.push_back('"');
 }
 
 // YMap (1) -> object, YText (2) -> string, XML types -> "" (XmlElement.toJSON is its XML text,

@@ -15,6 +15,7 @@
 #include <string>
 
 #include "yc_parse.h"  // YC_HD, yc_num.h
+#include "yc_str.h"    // ContentString pieces
 
 namespace yc {
 
@@ -51,8 +52,6 @@ struct JString {         // the host sink: appends to a string
   uint64_t n() const { return s.size(); }
 };
 
-YC_HDI uint32_t utf8_len(uint32_t c) { return c < 0x80u ? 1u : c < 0xE0u ? 2u : c < 0xF0u ? 3u : 4u; }
-
 template <class Sink>
 YC_HD inline void json_put_esc(Sink& o, const uint8_t* s, uint64_t n) {  // a JSON string's text without the quotes
   for (uint64_t i = 0; i < n; ++i) {
@@ -81,6 +80,12 @@ YC_HD inline void json_put_str(Sink& o, const uint8_t* s, uint64_t n) {
   o.ch('"');
   json_put_esc(o, s, n);
   o.ch('"');
+}
+
+// ... of a ContentString piece with its half pairs (yc_str.h): U+FFFD, which needs no escape
+template <class Sink>
+YC_HD inline void json_put_piece(Sink& o, const uint8_t* s, uint64_t n, uint32_t halves) {
+  str_put(s, n, halves, [&](uint32_t x) { o.ch(x); }, [&](const uint8_t* t, uint64_t k) { json_put_esc(o, t, k); });
 }
 
 template <class Sink>
@@ -272,10 +277,11 @@ YC_HD inline uint32_t any_json_text(const uint8_t* b, uint64_t& p, uint64_t end,
 
 // The elements of one visible view segment (its content bytes b[b0, b1), b0 <= b1 inside the
 // buffer), one per next(): ContentAny and ContentJSON hold `len` values, a ContentString one
-// element per UTF-8 character (a truncated tail clipped to the segment), ContentBinary,
+// element per UTF-8 character (a half pair at an edge of the piece, `halves`: U+FFFD, yc_str.h; a
+// tail truncated otherwise is clipped to the segment), ContentBinary,
 // ContentEmbed and ContentType one, a ContentFormat one `undefined` (getContent() is []), anything
 // else (ContentDoc is outside crdt.c) one null. `entry`: the value of a YMap entry, that is one
-// element — of a ContentString the last character, of an empty string nothing.
+// element — of a ContentString the last character (or half pair), of an empty string nothing.
 enum : uint32_t {
   EL_OK = 0,     // one element written
   EL_UNDEF = 1,  // the element is `undefined`: nothing written (an entry is omitted, a list member is null)
@@ -287,19 +293,35 @@ enum : uint32_t {
 struct SegCursor {
   JRd r;
   uint32_t ref, left, type_ref = 0;
-  YC_HDI SegCursor(const uint8_t* b, uint64_t b0, uint64_t b1, uint32_t ref_, uint32_t len, bool entry)
-      : r{b, b0, b1, true}, ref(ref_), left(ref_ == REF_ANY || ref_ == REF_JSON ? (entry ? 1u : len) : 1u) {
-    if (entry && ref == REF_STRING)  // (a string ends where its bytes end: `left` is not read)
-      for (uint64_t p = b0; p < b1; p += utf8_len(b[p])) r.p = p;
+  uint32_t head, tail;  // bytes of the piece's half pairs (ContentString)
+  YC_HDI SegCursor(const uint8_t* b, uint64_t b0, uint64_t b1, uint32_t ref_, uint32_t len, bool entry, uint32_t halves = 0)
+      : r{b, b0, b1, true}, ref(ref_), left(ref_ == REF_ANY || ref_ == REF_JSON ? (entry ? 1u : len) : 1u),
+        head(ref_ == REF_STRING ? str_head_len(halves, b1 - b0) : 0u), tail(ref_ == REF_STRING ? str_tail_len(halves, b1 - b0, head) : 0u) {
+    if (entry && ref == REF_STRING) {  // (a string ends where its bytes end: `left` is not read)
+      bool half;
+      for (uint64_t p = b0, h = head; p < b1; p += char_at(p, h, half), h = 0) r.p = p;
+      if (r.p != b0) head = 0;
+    }
+  }
+  // bytes of the character at p < r.end (`h`: a head half of h bytes stands there); half: it is U+FFFD
+  YC_HDI uint64_t char_at(uint64_t p, uint64_t h, bool& half) const {
+    half = h != 0;
+    if (h) return h;
+    uint64_t l = utf8_len(r.b[p]);
+    if (l > r.end - p) l = r.end - p;
+    half = tail && p + tail == r.end;
+    return l;
   }
   YC_HDI uint32_t stop(uint32_t e) { left = 0; r.p = r.end; return e; }
   template <class Sink, class Stack>
   YC_HD inline uint32_t next(Sink& o, Stack& st) {
     if (ref == REF_STRING) {
       if (r.p >= r.end) return EL_END;
-      uint64_t l = utf8_len(r.b[r.p]);
-      if (l > r.end - r.p) l = r.end - r.p;
-      json_put_str(o, r.b + r.p, l);
+      bool half;
+      const uint64_t l = char_at(r.p, head, half);
+      head = 0;
+      if (half) { o.ch('"'); for (uint32_t i = 0; i < 3; ++i) o.ch(fffd_byte(i)); o.ch('"'); }
+      else json_put_str(o, r.b + r.p, l);
       r.p += l;
       return EL_OK;
     }

@@ -89,7 +89,7 @@ __global__ void k_jindex(JsonArgs a) {
 // element followed by a separator, except the one that would stand where the container closes.
 __device__ __forceinline__ uint32_t emit_seg(const JsonArgs& a, const ViewSeg& s, bool entry, bool scans, JText& o, uint64_t cend) {
   if (s.b0 > s.b1 || s.b1 > a.nbytes) return EM_REFUSED;
-  SegCursor c(a.bytes, s.b0, s.b1, s.ref, s.len, entry);
+  SegCursor c(a.bytes, s.b0, s.b1, s.ref, s.len, entry, (s.flags >> VS_HALF_SHIFT) & 3u);
   uint32_t rem[ANY_JSON_DEPTH];
   JStack<ANY_JSON_DEPTH> st(rem);
   for (;;) {
@@ -153,7 +153,7 @@ __global__ void k_jsize(JsonArgs a, uint32_t round) {
       uint32_t t = 0;
       if (!(s.flags & VS_DELETED) && (s.flags & VS_ITEM) && s.ref == REF_STRING && s.b0 <= s.b1 && s.b1 <= a.nbytes) {
         JText q{nullptr, 0};
-        json_put_esc(q, a.bytes + s.b0, s.b1 - s.b0);
+        json_put_piece(q, a.bytes + s.b0, s.b1 - s.b0, (s.flags >> VS_HALF_SHIFT) & 3u);
         t = q.n > 0xFFFFFFF0ull ? 0u : (uint32_t)q.n;
         if (q.n > 0xFFFFFFF0ull) em = EM_REFUSED;
       }
@@ -300,7 +300,7 @@ __global__ void k_jwrite(JsonArgs a) {
   }
   const ViewSeg& s = a.segs[i - a.ck];
   if (end == NONE64) {  // a YText member: the escaped string between the type's quotes
-    json_put_esc(o, a.bytes + s.b0, s.b1 - s.b0);
+    json_put_piece(o, a.bytes + s.b0, s.b1 - s.b0, (s.flags >> VS_HALF_SHIFT) & 3u);
     return;
   }
   emit_seg(a, s, false, true, o, end);

@@ -486,10 +486,20 @@ __device__ uint32_t encode_event(const Work& w, uint32_t client, uint32_t e, uin
     const uint32_t nb = any_canon<WRITE>(w.bytes, w.s_celem[src], w.s_cend[src], off, off + len, out, p);
     size += vu_size(len) + nb;
   } else if (ref == REF_ANY || ref == REF_JSON || ref == REF_STRING) {
+    // mergeUpdates' sliceStruct splits: U+FFFD on both sides of a cut pair (str_copy); diffUpdate
+    // writes at the state vector's clock, and lib0 throws inside a pair
     uint32_t b0 = 0, b1 = 0;
-    if (!content_slice(w, src, off, off + len, b0, b1)) { raise_err(&w.ctr->err, ERR_UNSUPPORTED); return size; }
+    if (!content_slice(w, src, off, off + len, b0, b1, w.lz_diff != 0)) {
+      raise_err(&w.ctr->err, ERR_UNSUPPORTED);
+      if (ref == REF_STRING) w.ctr->err_info = ERRI_PAIR_OFFSET;
+      return size;
+    }
     const uint32_t pre = ref == REF_STRING ? b1 - b0 : len;
-    if (WRITE) { p = wr_vu(out, p, pre); for (uint32_t i = b0; i < b1; ++i) out[p++] = w.bytes[i]; }
+    if (WRITE) {
+      p = wr_vu(out, p, pre);
+      if (ref == REF_STRING) p = (uint32_t)str_copy(out, p, w.bytes + b0, b1 - b0);
+      else for (uint32_t i = b0; i < b1; ++i) out[p++] = w.bytes[i];
+    }
     size += vu_size(pre) + (b1 - b0);
   } else {
     const uint32_t n = w.s_cend[src] - w.s_cpos[src];

@@ -27,7 +27,7 @@ namespace {
 __device__ int32_t read_value(const JsonArgs& a, const ViewSeg& s, bool entry, uint32_t elem, JText& o, uint32_t& flags, Box& box,
                               bool& is_type) {
   is_type = false;
-  SegCursor c(a.bytes, s.b0, s.b1, s.ref, s.len, entry);
+  SegCursor c(a.bytes, s.b0, s.b1, s.ref, s.len, entry, (s.flags >> VS_HALF_SHIFT) & 3u);
   uint32_t rem[ANY_JSON_DEPTH];
   JStack<ANY_JSON_DEPTH> st(rem);
   JText skipped{nullptr, 0};

@@ -16,7 +16,7 @@
 namespace yc {
 namespace {
 
-constexpr uint32_t CUT_REFUSED = 0xFFFFFFFFu;  // content_slice_walk refuses the cut (inside a surrogate pair)
+constexpr uint32_t CUT_REFUSED = 0xFFFFFFFFu;  // the peer's clock falls inside a surrogate pair: Yjs throws (content_slice_walk, e0_write)
 constexpr uint32_t CUT_BAD = 0xFFFFFFFEu;      // the bytes are no struct that can be cut there
 
 __device__ __forceinline__ void sync_fail(SyncCtr* ctr, uint32_t dbg, uint32_t where) {
@@ -117,14 +117,15 @@ __device__ uint32_t cut_struct(const uint8_t* __restrict__ st, uint32_t pos, uin
   uint32_t celem = cpos;
   rd_vu(st, celem, cend, ok);  // the element count / the string's byte length
   if (!ok) return CUT_BAD;
-  const uint64_t r = content_slice_walk(st, ref, celem, cpos, cend, off, len);
+  const uint64_t r = content_slice_walk(st, ref, celem, cpos, cend, off, len, true);  // (off: the peer's clock)
   if (r == ~0ull) return CUT_REFUSED;
   const uint32_t b0 = (uint32_t)r, b1 = (uint32_t)(r >> 32);
   if (b0 > b1 || b1 > cend) return CUT_BAD;
   const uint32_t lead = ref == REF_STRING ? b1 - b0 : rem;
   if (WRITE) {
     q = wr_vu(out, q, lead);
-    for (uint32_t i = b0; i < b1; ++i) out[q++] = st[i];
+    if (ref == REF_STRING) str_copy(out, q, st + b0, b1 - b0);
+    else for (uint32_t i = b0; i < b1; ++i) out[q++] = st[i];
   }
   return size + vu_size(lead) + (b1 - b0);
 }

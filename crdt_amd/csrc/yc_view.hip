@@ -22,7 +22,8 @@ namespace yc {
 
 __device__ __forceinline__ bool countable_ref(uint32_t ref) { return ref != REF_DELETED && ref != REF_FORMAT; }
 
-// ViewSeg of segment s: every element, or only the last one (a YMap entry's value)
+// ViewSeg of segment s: every element, or only the last one (a YMap entry's value); of a
+// ContentString the piece, with its half pairs noted in the flags (VS_HALF_*)
 __device__ void fill_seg(const Work& w, uint32_t s, bool last_only, ViewSeg& v) {
   const uint32_t g0 = seg_start(w, s), g1 = seg_start(w, s + 1);
   const uint32_t cidx = w.g_cidx[s], own = w.g_src[s];
@@ -38,11 +39,14 @@ __device__ void fill_seg(const Work& w, uint32_t s, bool last_only, ViewSeg& v) 
   v.b0 = v.b1 = 0;
   if ((f & SEG_DEL) || !(f & SEG_ITEM)) return;
   const uint32_t e1 = clock + v.len - w.s_clock[own];
-  const uint32_t e0 = last_only ? e1 - 1 : clock - w.s_clock[own];
+  // (a string keeps the segment's whole piece, halves of a split surrogate pair included: SegCursor
+  // takes its last character, and its last unit may be half of one)
+  const uint32_t e0 = last_only && ref != REF_STRING ? e1 - 1 : clock - w.s_clock[own];
   uint32_t b0 = 0, b1 = 0;
   if (!content_slice(w, own, e0, e1, b0, b1)) { raise_err(&w.ctr->err, ERR_DECODE); return; }
   v.b0 = b0;
   v.b1 = b1;
+  if (ref == REF_STRING) v.flags |= str_halves(struct_bytes(w, own) + b0, b1 - b0) << VS_HALF_SHIFT;
 }
 
 __device__ void str_text(const Work& w, uint32_t pos, uint32_t len, uint32_t& tpos, uint32_t& tlen) {

@@ -6,6 +6,7 @@
 #pragma once
 #include <initializer_list>
 #include "yc_common.h"
+#include "yc_str.h"
 #include "yc_view.h"
 #include "yc_switches.h"
 
@@ -512,28 +513,35 @@ __device__ __forceinline__ const uint8_t* struct_bytes(const Work& w, uint32_t s
 // Byte range of content elements [e0, e1) of struct `src` (ContentAny: lib0 `any` values,
 // ContentJSON: varStrings, ContentString: UTF-16 code units of the UTF-8 text; every other
 // content has length 1 and is copied whole). This is ContentX.splice (Y@70000..) as a byte slice.
+// A ContentString edge between the two units of a surrogate pair yields 3 of the character's 4 bytes,
+// which every writer and reader takes for U+FFFD (yc_str.h) — unless the caller says that e0 is an
+// offset Yjs writes at (`e0_write`: a state vector's clock) and not a split it made: lib0 throws
+// there, and the slice is refused.
 // The element walk is out of line: inlined, the nested-`any` skipper multiplies the register
 // demand (and so cuts the occupancy) of every kernel that encodes structs, for a path that only
 // split structs take. The whole-content case stays inline.
 // (Plain values in, the range packed in a register pair out: a reference to Work or an
 // out-parameter would make every caller spill them to scratch memory on every path.)
 static __device__ __attribute__((noinline)) uint64_t content_slice_walk(const uint8_t* __restrict__ by, uint32_t ref, uint32_t celem,
-                                                                        uint32_t cpos, uint32_t end, uint32_t e0, uint32_t e1);
-__device__ __forceinline__ bool content_slice(const Work& w, uint32_t src, uint32_t e0, uint32_t e1, uint32_t& b0, uint32_t& b1) {
+                                                                        uint32_t cpos, uint32_t end, uint32_t e0, uint32_t e1,
+                                                                        bool e0_write);
+__device__ __forceinline__ bool content_slice(const Work& w, uint32_t src, uint32_t e0, uint32_t e1, uint32_t& b0, uint32_t& b1,
+                                              bool e0_write = false) {
   const uint32_t ref = w.s_info[src] & 31u;
   if (e0 == 0 && e1 == w.s_len[src] && (ref == REF_ANY || ref == REF_JSON)) {  // the whole content
     b0 = w.s_celem[src];
     b1 = w.s_cend[src];
     return true;
   }
-  const uint64_t r = content_slice_walk(struct_bytes(w, src), ref, w.s_celem[src], w.s_cpos[src], w.s_cend[src], e0, e1);
+  const uint64_t r = content_slice_walk(struct_bytes(w, src), ref, w.s_celem[src], w.s_cpos[src], w.s_cend[src], e0, e1, e0_write);
   if (r == ~0ull) return false;
   b0 = (uint32_t)r;
   b1 = (uint32_t)(r >> 32);
   return true;
 }
 static __device__ __attribute__((noinline)) uint64_t content_slice_walk(const uint8_t* __restrict__ by, uint32_t ref, uint32_t celem,
-                                                                        uint32_t cpos, uint32_t end, uint32_t e0, uint32_t e1) {
+                                                                        uint32_t cpos, uint32_t end, uint32_t e0, uint32_t e1,
+                                                                        bool e0_write) {
   uint32_t b0 = 0, b1 = 0;
   const bool got = [&]() -> bool {
   if (ref == REF_ANY || ref == REF_JSON) {
@@ -559,20 +567,11 @@ static __device__ __attribute__((noinline)) uint64_t content_slice_walk(const ui
     bool ok = true;
     rd_vu(by, p, end, ok);  // byte length prefix
     if (!ok) return false;
-    uint32_t u = 0;  // UTF-16 units before p
-    b0 = e0 == 0 ? p : NONE;
-    while (p < end && u < e1) {
-      const uint32_t c = by[p];
-      const uint32_t n = c < 0x80u ? 1u : c < 0xE0u ? 2u : c < 0xF0u ? 3u : 4u;
-      const uint32_t du = n == 4 ? 2u : 1u;
-      if (u < e0 && u + du > e0) return false;  // a slice through a surrogate pair
-      if (u < e1 && u + du > e1) return false;
-      p += n;
-      u += du;
-      if (u == e0) b0 = p;
-    }
-    b1 = p;
-    return b0 != NONE && u == e1;
+    const uint64_t r = str_slice(by, p, end, e0, e1, e0_write);
+    if (r == STR_REFUSED) return false;
+    b0 = (uint32_t)r;
+    b1 = (uint32_t)(r >> 32);
+    return true;
   }
   b0 = cpos;
   b1 = end;
@@ -672,6 +671,9 @@ __device__ __attribute__((noinline)) uint32_t any_canon(const uint8_t* __restric
 // Inline and without printf: a call in a kernel (even one never taken) makes it keep registers
 // across the call — k_units 38 -> 60 VGPRs — and a Work reference passed out of line copies the
 // whole Work to scratch in every lane (k_units / k_seg_props 20 x slower; tests/test_kernel_resources.py)
+// err_info of an ERR_UNSUPPORTED raised where Yjs would write a ContentString at an offset between the
+// two units of a surrogate pair (a state vector's clock there: lib0 throws); check() words the error
+constexpr uint32_t ERRI_PAIR_OFFSET = 0x5CA70001u;
 enum : uint32_t { BOUNDS_UNIT = 1, BOUNDS_KEY, BOUNDS_MERGE_SMALL, BOUNDS_ENCODE_SMALL, BOUNDS_OUTPUT, BOUNDS_DECODE_TAIL, BOUNDS_SECTIONS, BOUNDS_SYNC };
 __device__ __forceinline__ void bounds_fail(Counters* ctr, uint32_t what) {
   raise_err(&ctr->err, ERR_CAPACITY);
